@@ -21,7 +21,13 @@ are independent).  RCCL carries the C3 gradient all-reduce and th
 reductions.  Barrier + synchronize bracket the K timed steps; the time is the max over ranks; value =
 all ranks' reach-steps / that time.
 
-Usage:  python bench.py [--workload c5] [--gpus N] [--steps K] [--warmup W]
+A plain run sets up, warms up, times the K steps and prints the result line.  ``--full`` adds the legs
+that take runs of their own: the CPU baseline (``cpu_baseline``) and, for C5 on one GPU, the drop-in
+``dmc()`` path (``dropin_dmc``).  ``--dump-outputs DIR`` writes what the last timed step returned to its
+caller as ``DIR/<name>.npy`` (a fixed, seeded sample of rows where an array is large), so that two builds
+can be compared output for output: with the same arguments the inputs are the same from run to run.
+
+Usage:  python bench.py [--workload c5] [--gpus N] [--steps K] [--warmup W] [--full] [--dump-outputs DIR]
 """
 
 from __future__ import annotations
@@ -425,6 +431,12 @@ def main():
     ap.add_argument("--math", default=None, choices=["exact", "faithful", "fast"],
                     help="forward coefficient arithmetic (default faithful, the drop-in dmc's default -- "
                          "MuskingumCunge(math) -- and what the trainer runs; --fast-math = fast)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs that take runs of their own: the CPU baseline (--cpu-*, --no-cpu-baseline) "
+                         "and, for C5 on one GPU, the drop-in dmc() path (--dropin-steps)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write what the last timed step returned to its caller as DIR/<name>.npy (float32 / float64; "
+                         "a fixed, seeded sample of the rows of a large array)")
     args = ap.parse_args()
     args.math = args.math or ("fast" if args.fast_math else "faithful")
     spec = WORKLOADS[args.workload]
@@ -500,6 +512,8 @@ def main():
     # what its kernel moves is 4 B less per reach-step (reported beside it as kernel_bytes_per_reach_step)
     fwd_bytes, bwd_bytes = (8, 8) if args.workload == "c3" else (12, 12)
     bwd_kernel_bytes = bwd_bytes - 4
+    # --dump-outputs: the last timed step leaves here what its caller receives (keeping[0] is set before it)
+    keep, keeping = {}, [False]
 
     # ---- the step of each workload --------------------------------------------------------------------
     if args.workload == "c5":
@@ -516,6 +530,9 @@ def main():
             runoff, _, _, _ = route(g, qprime, n, q, p, length, slope, xs, consts=consts, math=args.math,
                                      exact_adjoint=args.exact_adjoint)
             runoff.backward(W)
+            if keeping[0]:
+                keep.update(runoff=runoff, grad_n=u_n.grad, grad_q_spatial=u_q.grad, grad_p_spatial=u_p.grad,
+                            grad_qprime=qprime.grad)
 
     elif args.workload == "c3":
         from ddr_amd.distributed import allreduce_gradients
@@ -543,6 +560,8 @@ def main():
             loss.backward()
             allreduce_gradients(list(model.parameters()))  # RCCL, one flat bucket
             opt.step()  # clip_grad_norm_(max_norm=1) + Adam (train.py:99-100)
+            if keeping[0]:
+                keep.update(daily=daily, loss=loss)
 
     else:
         from ddr_amd.geometry.statistics import geometry_statistics_from_inflow
@@ -551,9 +570,13 @@ def main():
 
         def step():
             with torch.no_grad():
+                stats = {}
                 if args.workload == "c4":  # first: the kernel timer reports the last forward launch
-                    geometry_statistics_from_inflow(g, qprime[::24][:365], n, p, q, slope)
-                route(g, qprime, n, q, p, length, slope, xs, consts=consts, save=False, math=args.math)
+                    stats = geometry_statistics_from_inflow(g, qprime[::24][:365], n, p, q, slope)
+                runoff, q_last, _, _ = route(g, qprime, n, q, p, length, slope, xs, consts=consts, save=False,
+                                             math=args.math)
+                if keeping[0]:
+                    keep.update(runoff=runoff, q_last=q_last, **{f"geometry_{k}": v for k, v in stats.items()})
 
     ev = []
     kms = {"forward": [], "backward": []}  # main routing kernels, HIP events on the launch stream
@@ -590,6 +613,7 @@ def main():
         for _ in range(2):
             timed_step()
         ev.clear()
+        keeping[0] = bool(args.dump_outputs)  # the captured step's outputs are the same tensors at every replay
         step = CapturedStep(step, warmup=1, device=dev)
         graph_mode = "whole step captured into one HIP graph (ddr_amd.capture); kernel ms from 2 eager steps"
         torch.cuda.synchronize()
@@ -598,6 +622,8 @@ def main():
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for i in range(args.steps):
+        if args.dump_outputs and i == args.steps - 1:
+            keeping[0] = True
         timed_step()
         log(f"[rank {rank}] step {i + 1}/{args.steps}")
     torch.cuda.synchronize()
@@ -607,6 +633,12 @@ def main():
     elapsed = time.perf_counter() - t0
     _lib.check(lib.ddr_set_kernel_timing(0))
     _lib.check(lib.ddr_status_check(1))  # any timed-out hand-off fails the run
+    keeping[0] = False
+    if args.dump_outputs:
+        if args.workload == "c3":  # the step's other result: the parameters after its update
+            keep["parameters"] = torch.cat([p_.detach().reshape(-1) for p_ in model.parameters()])
+        dump_outputs(args.dump_outputs, keep, "" if world == 1 else f".rank{rank}")
+    keep.clear()
     if args.block_profile and (rank == 0 or alone):
         block_profile(args.block_profile, g, step, lib)
 
@@ -648,9 +680,9 @@ def main():
                           None if split is None else (split.index, split.k))
         kc = (cf or {}).get("kernels", {}).get(f"route_{dom}_kernel", {})
         dropin = None
-        if args.workload == "c5" and world == 1 and args.dropin_steps > 0:
+        if args.full and args.workload == "c5" and world == 1 and args.dropin_steps > 0:
             dropin = time_dropin(args, net, at, u, qprime, W, dev)
-        cpu = None if (args.no_cpu_baseline or world > 1) else cpu_baseline(args, net, x_const)
+        cpu = None if (not args.full or args.no_cpu_baseline or world > 1) else cpu_baseline(args, net, x_const)
         if cpu is not None:
             cpu["speedup_vs_port"] = value / cpu["value"]
             cal = cpu.get("calibration")
@@ -878,6 +910,38 @@ def time_dropin(args, net, at, u, qprime, W, dev):
             "note": "dmc() forward + backward incl. setup_inputs (cached graph, hot start, PatternMapper)",
             "route_timestep_ms": bmi_ms,
             "route_timestep_note": f"BMI update: one MuskingumCunge.route_timestep (one hour, {net.n} reaches, no_grad), mean of {K}"}
+
+
+DUMP_ARRAY_BYTES = 16 << 20  # a larger array is written as a sample of its rows
+DUMP_TOTAL_BYTES = 64 * 10**6
+
+
+def dump_outputs(path, named, suffix=""):
+    """Write each output as ``<path>/<name><suffix>.npy`` in float32 (float64 where it is one).  An array above
+    16 MiB is written as a sample of its rows (axis 0): the same rows in every run, drawn without replacement
+    by a generator seeded with the row count, in ascending order.  At most 64 MB are written in all."""
+    out = Path(path)
+    out.mkdir(parents=True, exist_ok=True)
+    total = 0
+    for name, v in named.items():
+        if v is None:
+            continue
+        if not torch.is_tensor(v):
+            v = torch.from_numpy(np.ascontiguousarray(v))
+        v = v.detach()
+        dt = torch.float64 if v.dtype == torch.float64 else torch.float32
+        full_shape = tuple(v.shape)
+        item = 8 if dt == torch.float64 else 4
+        if v.dim() > 0 and v.numel() * item > DUMP_ARRAY_BYTES:
+            k = max(1, DUMP_ARRAY_BYTES // (v[0].numel() * item))
+            rows = np.sort(np.random.default_rng(v.shape[0]).choice(v.shape[0], size=k, replace=False))
+            v = v[torch.from_numpy(rows).to(v.device)]
+        a = v.to(dt).cpu().numpy()
+        total += a.nbytes
+        if total > DUMP_TOTAL_BYTES:
+            raise RuntimeError(f"--dump-outputs: more than {DUMP_TOTAL_BYTES} bytes of outputs ({name}: {a.shape})")
+        np.save(out / f"{name}{suffix}.npy", a)
+        log(f"[dump] {name}{suffix}.npy {a.dtype} {a.shape}" + (f", rows sampled of {full_shape}" if a.shape != full_shape else ""))
 
 
 def block_profile(path, g, step, lib):

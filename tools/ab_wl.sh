@@ -15,7 +15,7 @@ for size in ${WLS:-light c5}; do
       c3) fl="--workload c3 $C3FL";;
       *) fl="--workload $size";;
     esac
-    env $envs DDR_MC_LIB=$lib timeout -k 10 300 python $R/bench.py --steps 2 --warmup 1 --no-cpu-baseline --dropin-steps ${DROPIN:-0} $fl > $OUT/${v}_$size.log 2>&1 || { echo "$v $size failed"; tail -3 $OUT/${v}_$size.log; exit 1; }
+    env $envs DDR_MC_LIB=$lib timeout -k 10 300 python $R/bench.py --steps 2 --warmup 1 --full --no-cpu-baseline --dropin-steps ${DROPIN:-0} $fl > $OUT/${v}_$size.log 2>&1 || { echo "$v $size failed"; tail -3 $OUT/${v}_$size.log; exit 1; }
     echo "$v $size" $(grep '^{' $OUT/${v}_$size.log | python -c "import json,sys; d=json.loads(sys.stdin.read()); print(round(d['ms_per_step'],1), {k: round(v['kernel_ms'],2) for k, v in d['kernels'].items()}, d.get('dropin_dmc', {}).get('route_timestep_ms'))")
   done
 done

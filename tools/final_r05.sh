@@ -15,7 +15,7 @@ if [ "$STAGE" = a ]; then
   timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" > $OUT/smoke.log 2>&1 || { tail -5 $OUT/smoke.log; exit 1; }
   tail -1 $OUT/smoke.log
   bash $R/tools/bench_all.sh $TAG/bench || exit $?
-  ( time timeout -k 10 600 python $R/bench.py ) > $OUT/bench_default.log 2>&1 || { tail -5 $OUT/bench_default.log; exit 1; }
+  ( time timeout -k 10 600 python $R/bench.py --full ) > $OUT/bench_default.log 2>&1 || { tail -5 $OUT/bench_default.log; exit 1; }
   grep '^{' $OUT/bench_default.log > $OUT/bench_default.json; cut -c1-400 $OUT/bench_default.json
   cd /tmp && export TMPDIR=/tmp
   timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $OUT/prof -o run -- python3 $R/bench.py --steps 3 --warmup 1 --no-cpu-baseline --dropin-steps 0 > $OUT/rocprof_bench.log 2>&1 || exit $?

@@ -24,7 +24,7 @@ if [ "$STAGE" = b ]; then
   timeout -k 10 300 python3 -u $R/bench.py --workload c3 --steps 3 --warmup 1 --no-cpu-baseline --pnet torch --tail torch \
     > $OUT/bench_c3_torchcaller.json 2> $OUT/bench_c3_torchcaller.err || { tail -5 $OUT/bench_c3_torchcaller.err; exit 1; }
   cut -c1-300 $OUT/bench_c3_torchcaller.json
-  ( time timeout -k 10 600 python $R/bench.py ) > $OUT/bench_default.log 2>&1 || { tail -5 $OUT/bench_default.log; exit 1; }
+  ( time timeout -k 10 600 python $R/bench.py --full ) > $OUT/bench_default.log 2>&1 || { tail -5 $OUT/bench_default.log; exit 1; }
   grep '^{' $OUT/bench_default.log > $OUT/bench_default.json; cut -c1-400 $OUT/bench_default.json
   ( cd /tmp && export TMPDIR=/tmp && timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $OUT/prof -o run -- python3 $R/bench.py --steps 3 --warmup 1 --no-cpu-baseline --dropin-steps 0 > $OUT/rocprof_bench.log 2>&1 ) || exit 1
   python3 $R/tools/kstats.py $(find $OUT/prof -name "*.db") > $OUT/kernel_stats_c5.txt 2>&1

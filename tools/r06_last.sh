@@ -4,5 +4,5 @@ timeout -k 10 900 python -u -m pytest tests -m gpu -x -q --timeout 300 --timeout
 tail -1 $O/pytest.log
 timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1 || { tail -5 $O/smoke.log; exit 1; }
 grep smoke: $O/smoke.log
-timeout -k 10 600 python bench.py > $O/bench_default.log 2>&1 || { tail -5 $O/bench_default.log; exit 1; }
+timeout -k 10 600 python bench.py --full > $O/bench_default.log 2>&1 || { tail -5 $O/bench_default.log; exit 1; }
 grep '^{' $O/bench_default.log | cut -c1-300
