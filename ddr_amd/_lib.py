@@ -123,6 +123,7 @@ _SIGS = {
     "ddr_pnet_forward_f32": (C.c_int, [_I64, _I32, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "ddr_pnet_backward_f32": (C.c_int, [_I64, _I32, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "ddr_daily_l1_f32": (C.c_int, [_I64, _I64, _I64, _P, _P, C.c_float, _P, _P, _P]),
+    "ddr_metrics_f32": (C.c_int, [_I64, _I64, _P, _I64, _P, _I64, _P, _P, _P]),
     "ddr_clip_adam_work_bytes": (_I64, []),
     "ddr_clip_adam_f32": (C.c_int, [_I64, _P, _P, _P, _P, C.c_float, C.c_float, C.c_float, C.c_float, _P,
                                     C.c_float, _P, _P, _P]),

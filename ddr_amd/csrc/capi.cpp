@@ -11,6 +11,7 @@
 
 #include "internal.h"
 #include "route_args.h"
+#include "metrics.h"
 #include "train.h"
 
 namespace ddr {
@@ -556,6 +557,20 @@ ddr_status daily_l1_impl(int64_t n_gauges, int64_t n_days, int64_t warmup, const
   DDR_HIP(launch_daily_l1(n_gauges, n_days, warmup, daily, obs, inv_count, loss, grad, static_cast<hipStream_t>(stream)));
   return DDR_OK;
 }
+ddr_status metrics_impl(int64_t n_gauges, int64_t n_days, const float* pred, int64_t pred_stride, const float* target,
+                        int64_t target_stride, double* out, int32_t* pred_nan_count, void* stream) {
+  if (n_gauges < 0 || n_days < 0 || pred_stride < 0 || target_stride < 0)
+    return fail(DDR_ERR_ARG, "metrics: negative size");
+  if (n_gauges == 0) return DDR_OK;
+  if (n_days < 1 || n_days > kMetricsMaxDays)
+    return fail(DDR_ERR_ARG, "metrics: 1 <= n_days <= " + std::to_string(kMetricsMaxDays) + " (got " +
+                                 std::to_string(n_days) + ")");
+  if (n_gauges > INT32_MAX) return fail(DDR_ERR_ARG, "metrics: too many gauges");
+  if (!pred || !target || !out || !pred_nan_count) return fail(DDR_ERR_ARG, "metrics: null argument");
+  DDR_HIP(launch_metrics(n_gauges, n_days, pred, pred_stride, target, target_stride, out, pred_nan_count,
+                         static_cast<hipStream_t>(stream)));
+  return DDR_OK;
+}
 ddr_status clip_adam_impl(int64_t n, float* params, const float* grad, float* m, float* v, float lr, float beta1,
                           float beta2, float eps, float* step, float max_norm, float* norm_out, void* work,
                           void* stream) {
@@ -1078,6 +1093,11 @@ ddr_status ddr_pnet_backward_f32(int64_t n_rows, int32_t n_features, const float
 ddr_status ddr_daily_l1_f32(int64_t n_gauges, int64_t n_days, int64_t warmup, const float* daily, const float* obs,
                             float inv_count, float* loss, float* grad, void* stream) {
   DDR_GUARD({ return daily_l1_impl(n_gauges, n_days, warmup, daily, obs, inv_count, loss, grad, stream); })
+}
+ddr_status ddr_metrics_f32(int64_t n_gauges, int64_t n_days, const float* pred, int64_t pred_stride,
+                           const float* target, int64_t target_stride, double* out, int32_t* pred_nan_count,
+                           void* stream) {
+  DDR_GUARD({ return metrics_impl(n_gauges, n_days, pred, pred_stride, target, target_stride, out, pred_nan_count, stream); })
 }
 int64_t ddr_clip_adam_work_bytes(void) { return (int64_t)clip_adam_work_bytes(); }
 ddr_status ddr_clip_adam_f32(int64_t n, float* params, const float* grad, float* m, float* v, float lr, float beta1,

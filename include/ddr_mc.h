@@ -417,6 +417,44 @@ ddr_status ddr_geometry_stats_f32(const float* q_daily, int64_t reach_stride, in
                                   int64_t p_stride, const float* q_spatial, const float* slope,
                                   double depth_lb, double bottom_width_lb, float* out, void* stream);
 
+/* Per-gauge evaluation metrics of daily series (src/ddr/validation/metrics.py:11-256, the Metrics(pred, target)
+ * call of scripts/train.py:106-115 and scripts/test.py:107), one launch, no host sync, no allocation.
+ *   pred, target  device fp32, row g (a gauge) at pred + g * pred_stride / target + g * target_stride (strides in
+ *           elements, so a caller passes daily[:, warmup:] without a copy), 1 <= n_days <= 8192 values each.  A day
+ *           is valid when its target is not NaN.
+ *   out     device fp64 (DDR_N_METRICS, n_gauges), metric-major in the DDR_METRIC_* order below.  Sums, means,
+ *           roots and quotients are fp64 over the widened inputs, mean-dependent ones two-pass, in a fixed order:
+ *           a gauge's row does not depend on the other gauges of the launch.  Empty slices and zero denominators
+ *           follow IEEE (NaN, +-inf) like numpy; corr, corr_spearman, r2, nse, kge, kge_12 are NaN below two
+ *           valid days.
+ *   pred_nan_count  one device word, set to the number of NaN in pred (the reference's validator refuses them; a
+ *           gauge whose pred holds NaN gets unspecified values).
+ * n_gauges == 0 is a no-op. */
+enum {
+  DDR_METRIC_BIAS = 0,
+  DDR_METRIC_MAE,
+  DDR_METRIC_RMSE,
+  DDR_METRIC_UB_RMSE,
+  DDR_METRIC_FDC_RMSE,
+  DDR_METRIC_CORR,
+  DDR_METRIC_CORR_SPEARMAN,
+  DDR_METRIC_R2,
+  DDR_METRIC_NSE,
+  DDR_METRIC_FLV,
+  DDR_METRIC_FHV,
+  DDR_METRIC_PBIAS,
+  DDR_METRIC_PBIAS_MID,
+  DDR_METRIC_KGE,
+  DDR_METRIC_KGE_12,
+  DDR_METRIC_RMSE_LOW,
+  DDR_METRIC_RMSE_HIGH,
+  DDR_METRIC_RMSE_MID,
+  DDR_N_METRICS
+};
+ddr_status ddr_metrics_f32(int64_t n_gauges, int64_t n_days, const float* pred, int64_t pred_stride,
+                           const float* target, int64_t target_stride, double* out, int32_t* pred_nan_count,
+                           void* stream);
+
 /* Synchronise `stream` and read the device status block written by the last launches:
  * returns DDR_OK or DDR_ERR_TIMEOUT. */
 ddr_status ddr_graph_status(const void* status, void* stream);
