@@ -13,6 +13,10 @@ def __getattr__(name):
         from .routing.torch_mc import dmc
 
         return dmc
+    if name == "kan":
+        from .nn.kan import kan
+
+        return kan
     if name == "MuskingumCunge":
         from .routing.mmc import MuskingumCunge
 

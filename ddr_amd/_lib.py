@@ -76,6 +76,10 @@ class Gauges(C.Structure):
                 ("reach_offsets", C.c_void_p), ("reach_gauges", C.c_void_p)]
 
 
+class KanDesc(C.Structure):
+    _fields_ = [(name, C.c_int32) for name in ("n_features", "hidden", "n_outputs", "n_layers", "grid", "k")]
+
+
 _P = C.c_void_p
 _I64 = C.c_int64
 _I32 = C.c_int32
@@ -122,6 +126,11 @@ _SIGS = {
     "ddr_pnet_work_bytes": (_I64, [_I64, _I32]),
     "ddr_pnet_forward_f32": (C.c_int, [_I64, _I32, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "ddr_pnet_backward_f32": (C.c_int, [_I64, _I32, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "ddr_kan_param_count": (_I64, [C.POINTER(KanDesc)]),
+    "ddr_kan_const_count": (_I64, [C.POINTER(KanDesc)]),
+    "ddr_kan_work_bytes": (_I64, [C.POINTER(KanDesc), _I64, _I32]),
+    "ddr_kan_forward_f32": (C.c_int, [C.POINTER(KanDesc), _I64, _P, _P, _P, _P, _P, _P, _P]),
+    "ddr_kan_backward_f32": (C.c_int, [C.POINTER(KanDesc), _I64, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "ddr_daily_l1_f32": (C.c_int, [_I64, _I64, _I64, _P, _P, C.c_float, _P, _P, _P]),
     "ddr_metrics_f32": (C.c_int, [_I64, _I64, _P, _I64, _P, _I64, _P, _P, _P]),
     "ddr_clip_adam_work_bytes": (_I64, []),

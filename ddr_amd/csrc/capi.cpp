@@ -13,6 +13,7 @@
 #include "route_args.h"
 #include "metrics.h"
 #include "train.h"
+#include "kan.h"
 
 namespace ddr {
 
@@ -547,6 +548,34 @@ ddr_status pnet_backward_impl(int64_t n_rows, int32_t n_features, const float* x
   const float* g[3] = {grad_n, grad_q, grad_p};
   DDR_HIP(launch_pnet_backward(n_rows, n_features, x, params, denorm, z_save, u_save, g, grad_params, work,
                                static_cast<hipStream_t>(stream)));
+  return DDR_OK;
+}
+
+// kan.hip: descriptor and pointer checks of the KAN entry points (the envelope itself: kan_validate, kan.h)
+ddr_status kan_check(const ddr_kan_desc* desc, int64_t n_rows) {
+  const std::string why = kan_validate(desc);
+  if (!why.empty()) return fail(DDR_ERR_ARG, why);
+  if (n_rows < 1 || n_rows > (int64_t(1) << 30)) return fail(DDR_ERR_ARG, "kan: 1 <= rows <= 2^30");
+  return DDR_OK;
+}
+ddr_status kan_forward_impl(const ddr_kan_desc* desc, int64_t n_rows, const float* x, const float* params,
+                            const float* consts, float* h_save, float* u, void* work, void* stream) {
+  ddr_status st = kan_check(desc, n_rows);
+  if (st) return st;
+  if (!x || !params || !consts || !u) return fail(DDR_ERR_ARG, "kan: null argument");
+  if (!h_save && desc->n_layers > 1 && !work) return fail(DDR_ERR_ARG, "kan: work is needed when nothing is saved");
+  DDR_HIP(launch_kan_forward(*desc, n_rows, x, params, consts, h_save, u, work, static_cast<hipStream_t>(stream)));
+  return DDR_OK;
+}
+ddr_status kan_backward_impl(const ddr_kan_desc* desc, int64_t n_rows, const float* x, const float* params,
+                             const float* consts, const float* h_save, const float* u, const float* grad_u,
+                             float* grad_params, void* work, void* stream) {
+  ddr_status st = kan_check(desc, n_rows);
+  if (st) return st;
+  if (!x || !params || !consts || !h_save || !u || !grad_u || !grad_params || !work)
+    return fail(DDR_ERR_ARG, "kan: null argument");
+  DDR_HIP(launch_kan_backward(*desc, n_rows, x, params, consts, h_save, u, grad_u, grad_params, work,
+                              static_cast<hipStream_t>(stream)));
   return DDR_OK;
 }
 
@@ -1089,6 +1118,27 @@ ddr_status ddr_pnet_backward_f32(int64_t n_rows, int32_t n_features, const float
                                  const float* grad_q, const float* grad_p, float* grad_params, void* work,
                                  void* stream) {
   DDR_GUARD({ return pnet_backward_impl(n_rows, n_features, x, params, denorm, z_save, u_save, grad_n, grad_q, grad_p, grad_params, work, stream); })
+}
+int64_t ddr_kan_param_count(const ddr_kan_desc* desc) {
+  if (!kan_validate(desc).empty()) return -1;
+  return KanLayout(*desc).total();
+}
+int64_t ddr_kan_const_count(const ddr_kan_desc* desc) {
+  if (!kan_validate(desc).empty()) return -1;
+  return KanLayout(*desc).const_total();
+}
+int64_t ddr_kan_work_bytes(const ddr_kan_desc* desc, int64_t n_rows, int32_t backward) {
+  if (!kan_validate(desc).empty() || n_rows < 1 || n_rows > (int64_t(1) << 30)) return -1;
+  return kan_work_bytes(*desc, n_rows, backward != 0);
+}
+ddr_status ddr_kan_forward_f32(const ddr_kan_desc* desc, int64_t n_rows, const float* x, const float* params,
+                               const float* consts, float* h_save, float* u, void* work, void* stream) {
+  DDR_GUARD({ return kan_forward_impl(desc, n_rows, x, params, consts, h_save, u, work, stream); })
+}
+ddr_status ddr_kan_backward_f32(const ddr_kan_desc* desc, int64_t n_rows, const float* x, const float* params,
+                                const float* consts, const float* h_save, const float* u, const float* grad_u,
+                                float* grad_params, void* work, void* stream) {
+  DDR_GUARD({ return kan_backward_impl(desc, n_rows, x, params, consts, h_save, u, grad_u, grad_params, work, stream); })
 }
 ddr_status ddr_daily_l1_f32(int64_t n_gauges, int64_t n_days, int64_t warmup, const float* daily, const float* obs,
                             float inv_count, float* loss, float* grad, void* stream) {

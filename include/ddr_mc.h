@@ -361,6 +361,43 @@ ddr_status ddr_pnet_backward_f32(int64_t n_rows, int32_t n_features, const float
                                  const float* grad_q, const float* grad_p, float* grad_params, void* work,
                                  void* stream);
 
+/* The reference's parameter network (src/ddr/nn/kan.py:11-62): attributes x (n_rows, F) -> Linear(F, H) ->
+ * L pykan KAN([H, H]) layers (grid G, order k, symbolic branch off) -> Linear(H, O) -> sigmoid -> u (n_rows, O)
+ * in [0, 1]; the denormalisation stays with the routing engine, as in the reference.  One persistent launch
+ * per KAN layer with the Linears fused in (csrc/kan.hip), against ~40 PyTorch launches per layer and an
+ * (n_rows, H, G + k) basis tensor.
+ * Supported: 1 <= F <= 32, 1 <= H <= 32, 1 <= O <= 8, 1 <= L <= 4, 1 <= k <= 3, G >= 1,
+ * H H (G + k) <= 32768, 1 <= n_rows <= 2^30, every knot row strictly increasing (the caller's to check: the
+ * knots are device memory); anything else is DDR_ERR_ARG with a message naming the limit.
+ *   params  flat fp32, ddr_kan_param_count values: input.weight (H, F) | input.bias (H) | per layer: coef
+ *           (H, H, G + k) [in, out, j] | scale_base (H, H) [in, out] | scale_sp (H, H) | output.weight (O, H) |
+ *           output.bias (O)
+ *   consts  flat fp32, ddr_kan_const_count values, per layer: grid (H, G + 1 + 2k) | mask (H, H) [in, out] |
+ *           node_scale (H) | node_bias (H) | subnode_scale (H) | subnode_bias (H)
+ *   h_save  (L + 1, n_rows, H): the input Linear's output and every layer's output, kept for the backward;
+ *           NULL (inference) saves nothing, and the layers' activations pass through `work`
+ *   work    device scratch of ddr_kan_work_bytes(desc, n_rows, backward) bytes
+ *   grad_params (layout of params) = dL/dparams given grad_u = dL/du (n_rows, O); no gradient of x.
+ *           Bitwise reproducible: no atomics, per-workgroup partials summed in a fixed order.
+ * Replaces: ddr.nn.kan's forward (kan.py:50-62, pykan's MultKAN.forward / KANLayer.forward / B_batch) and its
+ * torch autograd in scripts/train.py:54-104. */
+typedef struct ddr_kan_desc {
+  int32_t n_features; /* F */
+  int32_t hidden;     /* H */
+  int32_t n_outputs;  /* O */
+  int32_t n_layers;   /* L */
+  int32_t grid;       /* G */
+  int32_t k;
+} ddr_kan_desc;
+int64_t ddr_kan_param_count(const ddr_kan_desc* desc);
+int64_t ddr_kan_const_count(const ddr_kan_desc* desc);
+int64_t ddr_kan_work_bytes(const ddr_kan_desc* desc, int64_t n_rows, int32_t backward);
+ddr_status ddr_kan_forward_f32(const ddr_kan_desc* desc, int64_t n_rows, const float* x, const float* params,
+                               const float* consts, float* h_save, float* u, void* work, void* stream);
+ddr_status ddr_kan_backward_f32(const ddr_kan_desc* desc, int64_t n_rows, const float* x, const float* params,
+                                const float* consts, const float* h_save, const float* u, const float* grad_u,
+                                float* grad_params, void* work, void* stream);
+
 /* The tail of a training step (scripts/train.py:91-100), one launch each, device pointers on `stream`:
  * ddr_daily_l1_f32: loss[0] = inv_count * sum_{g, d >= warmup} |daily[g, d] - obs[g, d]| over (G, D) row-major
  *   series, and (grad != NULL) grad[g, d] = inv_count * sign(daily - obs), 0 for d < warmup -- l1_loss
