@@ -80,6 +80,11 @@ class KanDesc(C.Structure):
     _fields_ = [(name, C.c_int32) for name in ("n_features", "hidden", "n_outputs", "n_layers", "grid", "k")]
 
 
+class GeomSlot(C.Structure):
+    _fields_ = [("column", C.c_int32), ("log_space", C.c_int32), ("lo", C.c_double), ("hi", C.c_double),
+                ("value", C.c_double)]
+
+
 _P = C.c_void_p
 _I64 = C.c_int64
 _I32 = C.c_int32
@@ -133,6 +138,10 @@ _SIGS = {
     "ddr_kan_backward_f32": (C.c_int, [C.POINTER(KanDesc), _I64, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "ddr_daily_l1_f32": (C.c_int, [_I64, _I64, _I64, _P, _P, C.c_float, _P, _P, _P]),
     "ddr_metrics_f32": (C.c_int, [_I64, _I64, _P, _I64, _P, _I64, _P, _P, _P]),
+    "ddr_attr_prepare_f32": (C.c_int, [_I64, _I32, _P, _I64, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "ddr_geometry_predict_f32": (C.c_int, [_I64, _I32, _P, C.POINTER(GeomSlot), C.POINTER(GeomSlot),
+                                           C.POINTER(GeomSlot), _P, _P, C.c_double, C.c_double, C.c_double,
+                                           C.c_double, _P, _I64, _P]),
     "ddr_clip_adam_work_bytes": (_I64, []),
     "ddr_clip_adam_f32": (C.c_int, [_I64, _P, _P, _P, _P, C.c_float, C.c_float, C.c_float, C.c_float, _P,
                                     C.c_float, _P, _P, _P]),

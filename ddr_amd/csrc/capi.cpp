@@ -14,6 +14,7 @@
 #include "metrics.h"
 #include "train.h"
 #include "kan.h"
+#include "geopredict.h"
 
 namespace ddr {
 
@@ -576,6 +577,72 @@ ddr_status kan_backward_impl(const ddr_kan_desc* desc, int64_t n_rows, const flo
     return fail(DDR_ERR_ARG, "kan: null argument");
   DDR_HIP(launch_kan_backward(*desc, n_rows, x, params, consts, h_save, u, grad_u, grad_params, work,
                               static_cast<hipStream_t>(stream)));
+  return DDR_OK;
+}
+
+// geopredict.hip: the geometry predictor's two launches
+ddr_status attr_prepare_impl(int64_t n_rows, int32_t n_features, const float* raw, int64_t feat_stride,
+                             const double* scale, const double* offset, const int32_t* log10_flag, const float* mean,
+                             const float* std, const float* p10, const float* p90, float* x, int64_t* counts,
+                             void* stream) {
+  if (n_rows < 0 || feat_stride < 0) return fail(DDR_ERR_ARG, "attr_prepare: negative size");
+  if (n_features < 1 || n_features > kGeoMaxF)
+    return fail(DDR_ERR_ARG, "attr_prepare: 1 <= n_features <= " + std::to_string(kGeoMaxF) + " (got " +
+                                 std::to_string(n_features) + ")");
+  if (n_rows == 0) return DDR_OK;
+  if (n_rows > kGeoMaxRows) return fail(DDR_ERR_ARG, "attr_prepare: too many rows");
+  if (feat_stride < n_rows && n_features > 1)
+    return fail(DDR_ERR_ARG, "attr_prepare: feat_stride is shorter than a column");
+  if (!raw || !scale || !offset || !log10_flag || !mean || !std || !x)
+    return fail(DDR_ERR_ARG, "attr_prepare: null argument");
+  if ((p10 == nullptr) != (p90 == nullptr)) return fail(DDR_ERR_ARG, "attr_prepare: p10 and p90 go together");
+  if (p10 && !counts) return fail(DDR_ERR_ARG, "attr_prepare: null counts with p10 / p90");
+  DDR_HIP(launch_attr_prepare(n_rows, n_features, raw, feat_stride, scale, offset, log10_flag, mean, std, p10, p90,
+                              x, reinterpret_cast<long long*>(counts), static_cast<hipStream_t>(stream)));
+  return DDR_OK;
+}
+// denormalize's scalars as torch holds them (routing/utils.py:177-185: fp32 tensors of bounds[0] + 1e-6 and
+// bounds[1], their fp32 logs, and Python-double differences rounded when they meet the fp32 tensor)
+GeoSlot geom_slot(const ddr_geom_slot& s) {
+  GeoSlot g{s.column, s.log_space, 0.0f, 0.0f, (float)s.value};
+  if (s.log_space) {
+    const float log_lo = std::log((float)(s.lo + 1e-6)), log_hi = std::log((float)s.hi);
+    g.a = log_hi - log_lo;
+    g.b = log_lo;
+  } else {
+    g.a = (float)(s.hi - s.lo);
+    g.b = (float)s.lo;
+  }
+  return g;
+}
+ddr_status geometry_predict_impl(int64_t n_rows, int32_t n_outputs, const float* u, const ddr_geom_slot* slot_n,
+                                 const ddr_geom_slot* slot_q, const ddr_geom_slot* slot_p, const float* discharge,
+                                 const float* slope, double discharge_lb, double slope_lb, double depth_lb,
+                                 double bottom_width_lb, float* out, int64_t out_stride, void* stream) {
+  if (n_rows < 0 || out_stride < 0) return fail(DDR_ERR_ARG, "geometry_predict: negative size");
+  if (n_outputs < 1 || n_outputs > kKanMaxO)
+    return fail(DDR_ERR_ARG, "geometry_predict: 1 <= n_outputs <= " + std::to_string(kKanMaxO) + " (got " +
+                                 std::to_string(n_outputs) + ")");
+  if (!slot_n || !slot_q || !slot_p) return fail(DDR_ERR_ARG, "geometry_predict: null slot");
+  const ddr_geom_slot* slots[3] = {slot_n, slot_q, slot_p};
+  const char* names[3] = {"n", "q_spatial", "p_spatial"};
+  for (int k = 0; k < 3; ++k) {
+    if (slots[k]->column >= n_outputs || slots[k]->column < -1)
+      return fail(DDR_ERR_ARG, std::string("geometry_predict: the column of ") + names[k] + " is outside u (" +
+                                   std::to_string(slots[k]->column) + " of " + std::to_string(n_outputs) + ")");
+    if (k < 2 && slots[k]->column < 0)
+      return fail(DDR_ERR_ARG, std::string("geometry_predict: ") + names[k] + " has no default: it needs a column of u");
+  }
+  if (n_rows == 0) return DDR_OK;
+  if (n_rows > kGeoMaxRows) return fail(DDR_ERR_ARG, "geometry_predict: too many rows");
+  if (!u || !out) return fail(DDR_ERR_ARG, "geometry_predict: null argument");
+  if ((discharge == nullptr) != (slope == nullptr))
+    return fail(DDR_ERR_ARG, "geometry_predict: null discharge or slope (both NULL: parameters only)");
+  if (out_stride < n_rows) return fail(DDR_ERR_ARG, "geometry_predict: out_stride is shorter than a row");
+  const GeoSlot gs[3] = {geom_slot(*slot_n), geom_slot(*slot_q), geom_slot(*slot_p)};
+  DDR_HIP(launch_geometry_predict(n_rows, n_outputs, u, gs, discharge, slope, (float)discharge_lb, (float)slope_lb,
+                                  (float)depth_lb, (float)bottom_width_lb, out, out_stride,
+                                  static_cast<hipStream_t>(stream)));
   return DDR_OK;
 }
 
@@ -1148,6 +1215,18 @@ ddr_status ddr_metrics_f32(int64_t n_gauges, int64_t n_days, const float* pred, 
                            const float* target, int64_t target_stride, double* out, int32_t* pred_nan_count,
                            void* stream) {
   DDR_GUARD({ return metrics_impl(n_gauges, n_days, pred, pred_stride, target, target_stride, out, pred_nan_count, stream); })
+}
+ddr_status ddr_attr_prepare_f32(int64_t n_rows, int32_t n_features, const float* raw, int64_t feat_stride,
+                                const double* scale, const double* offset, const int32_t* log10_flag,
+                                const float* mean, const float* std, const float* p10, const float* p90, float* x,
+                                int64_t* counts, void* stream) {
+  DDR_GUARD({ return attr_prepare_impl(n_rows, n_features, raw, feat_stride, scale, offset, log10_flag, mean, std, p10, p90, x, counts, stream); })
+}
+ddr_status ddr_geometry_predict_f32(int64_t n_rows, int32_t n_outputs, const float* u, const ddr_geom_slot* slot_n,
+                                    const ddr_geom_slot* slot_q, const ddr_geom_slot* slot_p, const float* discharge,
+                                    const float* slope, double discharge_lb, double slope_lb, double depth_lb,
+                                    double bottom_width_lb, float* out, int64_t out_stride, void* stream) {
+  DDR_GUARD({ return geometry_predict_impl(n_rows, n_outputs, u, slot_n, slot_q, slot_p, discharge, slope, discharge_lb, slope_lb, depth_lb, bottom_width_lb, out, out_stride, stream); })
 }
 int64_t ddr_clip_adam_work_bytes(void) { return (int64_t)clip_adam_work_bytes(); }
 ddr_status ddr_clip_adam_f32(int64_t n, float* params, const float* grad, float* m, float* v, float lr, float beta1,

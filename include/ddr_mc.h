@@ -492,6 +492,73 @@ ddr_status ddr_metrics_f32(int64_t n_gauges, int64_t n_days, const float* pred, 
                            const float* target, int64_t target_stride, double* out, int32_t* pred_nan_count,
                            void* stream);
 
+/* The geometry predictor around the KAN (src/ddr/geometry/predictor.py, adapters.py): two launches that with
+ * ddr_kan_forward_f32 between them take raw catchment attributes to channel geometry.  Device pointers, fp32
+ * unless stated, no host sync, no allocation; n_rows == 0 is a no-op.
+ *
+ * ddr_attr_prepare_f32: raw attributes -> the KAN's input x (n_rows, n_features) row-major.
+ *   raw     n_features columns of n_rows floats, feature f at raw + f * feat_stride (elements)
+ *   scale, offset (fp64), log10_flag (int32)  per feature: the source's unit conversion.  A feature with
+ *           scale != 1, offset != 0 or the flag set is converted in fp64, w = (double)v * scale + offset,
+ *           flagged: w = log10(max(w, 1e-6)) (NaN kept), and rounded to fp32 (adapters.py:159-162); any other
+ *           feature passes unchanged
+ *   p10, p90  both NULL or both given: counts[1][f] += (v < p10[f]), counts[2][f] += (v > p90[f]) on the
+ *           converted value; a NaN is neither (predictor.py:320-350)
+ *   mean, std  a NaN v becomes mean[f] and counts[0][f] += 1 (predictor.py:254-262; +-inf is left alone), then
+ *           x[i][f] = (v - mean[f]) / std[f]: an fp32 subtraction and an IEEE division (predictor.py:270), so a
+ *           zero std gives +-inf or NaN as the reference's does (std is device memory: not checked here)
+ *   counts  NULL, or int64 (3, n_features) = filled, below, above, which the CALLER zeroes: integer atomics, one
+ *           per counter and workgroup, so the totals are exact and independent of the order
+ *   1 <= n_features <= 32 (the KAN's envelope).
+ * Replaces: adapt_attributes' conversion, _check_distribution, _prepare_attributes (np.isnan / fill / stack /
+ * subtract / divide / transpose: ~5 passes over (F, N) on the host and 3 launches).
+ *
+ * ddr_geometry_predict_f32: the KAN's output u (n_rows, n_outputs) in [0, 1] -> parameters and geometry.
+ *   slot_n, slot_q, slot_p  where n, q_spatial and p_spatial come from: column of u (or -1: `value`,
+ *           p_spatial only -- the reference has no default for the others, predictor.py:307-316), the bounds
+ *           lo / hi and the log-space flag of denormalize (routing/utils.py:166-185): u (hi - lo) + lo, or
+ *           exp(u (log(hi) - log(lo + 1e-6)) + log(lo + 1e-6)); every scalar is rounded to fp32 on the host
+ *           before it is used, as torch's fp32 scalar tensors are
+ *   discharge, slope  (n_rows) each, clamped from below by discharge_lb / slope_lb with torch.clamp's NaN
+ *           rule (NaN stays NaN, predictor.py:211-214): a reach with a NaN slope or discharge gets its n / p / q
+ *           and NaN in the eight geometry rows
+ *   out     DDR_N_GEOM rows of out_stride >= n_rows floats in the DDR_GEOM_* order below (the reference's
+ *           order, predictor.py:216-238): compute_trapezoidal_geometry (trapezoidal.py:62-97) in its operation
+ *           order with IEEE division and square root, correctly rounded pow and the fixed side-slope clamp
+ *           [0.5, 50]
+ *   discharge == NULL and slope == NULL: parameters only -- out is three rows n, p_spatial, q_spatial
+ *           (_predict_parameters, predictor.py:276-318), the same bits as rows DDR_GEOM_N.. of a full call.
+ * Replaces: three denormalize calls, two clamps and the ~25 element-wise launches of
+ * compute_trapezoidal_geometry, each over (n_rows,) temporaries. */
+enum {
+  DDR_GEOM_DEPTH = 0,
+  DDR_GEOM_TOP_WIDTH,
+  DDR_GEOM_BOTTOM_WIDTH,
+  DDR_GEOM_SIDE_SLOPE,
+  DDR_GEOM_CROSS_SECTIONAL_AREA,
+  DDR_GEOM_WETTED_PERIMETER,
+  DDR_GEOM_HYDRAULIC_RADIUS,
+  DDR_GEOM_VELOCITY,
+  DDR_GEOM_N,
+  DDR_GEOM_P_SPATIAL,
+  DDR_GEOM_Q_SPATIAL,
+  DDR_N_GEOM
+};
+typedef struct ddr_geom_slot {
+  int32_t column;    /* column of u, or -1: `value` */
+  int32_t log_space; /* denormalize's log_space */
+  double lo, hi;     /* the parameter's range */
+  double value;      /* the default of a slot without a column */
+} ddr_geom_slot;
+ddr_status ddr_attr_prepare_f32(int64_t n_rows, int32_t n_features, const float* raw, int64_t feat_stride,
+                                const double* scale, const double* offset, const int32_t* log10_flag,
+                                const float* mean, const float* std, const float* p10, const float* p90, float* x,
+                                int64_t* counts, void* stream);
+ddr_status ddr_geometry_predict_f32(int64_t n_rows, int32_t n_outputs, const float* u, const ddr_geom_slot* slot_n,
+                                    const ddr_geom_slot* slot_q, const ddr_geom_slot* slot_p, const float* discharge,
+                                    const float* slope, double discharge_lb, double slope_lb, double depth_lb,
+                                    double bottom_width_lb, float* out, int64_t out_stride, void* stream);
+
 /* Synchronise `stream` and read the device status block written by the last launches:
  * returns DDR_OK or DDR_ERR_TIMEOUT. */
 ddr_status ddr_graph_status(const void* status, void* stream);
