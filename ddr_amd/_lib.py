@@ -138,6 +138,10 @@ _SIGS = {
     "ddr_kan_backward_f32": (C.c_int, [C.POINTER(KanDesc), _I64, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "ddr_daily_l1_f32": (C.c_int, [_I64, _I64, _I64, _P, _P, C.c_float, _P, _P, _P]),
     "ddr_metrics_f32": (C.c_int, [_I64, _I64, _P, _I64, _P, _I64, _P, _P, _P]),
+    "ddr_summedq_plan_create": (C.c_int, [_I64, _P, _P, _I64, _P, C.POINTER(C.c_void_p)]),
+    "ddr_summedq_plan_destroy": (C.c_int, [_P]),
+    "ddr_summedq_scratch_bytes": (_I64, [_P, _I64]),
+    "ddr_summedq_f32": (C.c_int, [_P, _P, _I64, _I64, _I64, _I32, _P, _I64, _P, _I64, _P]),
     "ddr_attr_prepare_f32": (C.c_int, [_I64, _I32, _P, _I64, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "ddr_geometry_predict_f32": (C.c_int, [_I64, _I32, _P, C.POINTER(GeomSlot), C.POINTER(GeomSlot),
                                            C.POINTER(GeomSlot), _P, _P, C.c_double, C.c_double, C.c_double,

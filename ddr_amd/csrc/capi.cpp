@@ -15,6 +15,7 @@
 #include "train.h"
 #include "kan.h"
 #include "geopredict.h"
+#include "summedq.h"
 
 namespace ddr {
 
@@ -1215,6 +1216,28 @@ ddr_status ddr_metrics_f32(int64_t n_gauges, int64_t n_days, const float* pred, 
                            const float* target, int64_t target_stride, double* out, int32_t* pred_nan_count,
                            void* stream) {
   DDR_GUARD({ return metrics_impl(n_gauges, n_days, pred, pred_stride, target, target_stride, out, pred_nan_count, stream); })
+}
+ddr_status ddr_summedq_plan_create(int64_t n_gauges, const int64_t* member_off, const int32_t* member_idx,
+                                   int64_t chunk, void* stream, ddr_summedq_plan* plan) {
+  DDR_GUARD({
+    return summedq_plan_create(n_gauges, member_off, member_idx, chunk, static_cast<hipStream_t>(stream),
+                               reinterpret_cast<SummedQPlan**>(plan));
+  })
+}
+ddr_status ddr_summedq_plan_destroy(ddr_summedq_plan plan) {
+  summedq_plan_destroy(static_cast<SummedQPlan*>(plan));
+  return DDR_OK;
+}
+int64_t ddr_summedq_scratch_bytes(ddr_summedq_plan plan, int64_t n_days) {
+  return summedq_scratch_bytes(static_cast<const SummedQPlan*>(plan), n_days);
+}
+ddr_status ddr_summedq_f32(ddr_summedq_plan plan, const float* qr, int64_t n_rows, int64_t row_stride, int64_t n_steps,
+                           int32_t hours_per_step, float* out, int64_t out_stride, void* scratch,
+                           int64_t scratch_bytes, void* stream) {
+  DDR_GUARD({
+    return summedq_run(static_cast<const SummedQPlan*>(plan), qr, n_rows, row_stride, n_steps, hours_per_step, out,
+                       out_stride, scratch, scratch_bytes, static_cast<hipStream_t>(stream));
+  })
 }
 ddr_status ddr_attr_prepare_f32(int64_t n_rows, int32_t n_features, const float* raw, int64_t feat_stride,
                                 const double* scale, const double* offset, const int32_t* log10_flag,

@@ -1,5 +1,7 @@
-"""Evaluation metrics on the device (mirrors ``ddr.validation``; the plots and ``log_metrics`` stay host code)."""
+"""Evaluation on the device (mirrors ``ddr.validation``; the plots and ``log_metrics`` stay host code): the
+per-gauge metrics and the summed-Q' baseline they are read against."""
 
 from .metrics import METRIC_NAMES, Metrics, metrics_device
+from .summed_q_prime import SummedQPrime, members_from_ids, summed_q_prime_metrics
 
-__all__ = ["METRIC_NAMES", "Metrics", "metrics_device"]
+__all__ = ["METRIC_NAMES", "Metrics", "metrics_device", "SummedQPrime", "members_from_ids", "summed_q_prime_metrics"]

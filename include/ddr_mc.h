@@ -492,6 +492,44 @@ ddr_status ddr_metrics_f32(int64_t n_gauges, int64_t n_days, const float* pred, 
                            const float* target, int64_t target_stride, double* out, int32_t* pred_nan_count,
                            void* stream);
 
+/* The summed-Q' baseline of the evaluation (scripts/summed_q_prime.py:208-261, eval_q_prime): per gauge and day
+ * the sum of the lateral inflow of the gauge's upstream divides, the unrouted series that routed results are
+ * scored against.  With rho = hours_per_step (24: hourly store, 1: daily store) and D = n_steps / rho (trailing
+ * steps that do not fill a day are dropped),
+ *   daily[i][d] = (sum_{h < rho} qr[i][d * rho + h]) / rho      a plain mean: one NaN hour makes the day NaN
+ *   out[g][d]   = sum over the members i of gauge g whose daily[i][d] is not NaN of daily[i][d]      (nansum)
+ * An empty list, or a day on which every member is NaN, gives 0; +-inf follows IEEE.  Every sum and the division
+ * run in fp64 over the fp32 inputs in an order fixed by the member's position in its list, and the result is
+ * rounded once to fp32: a gauge's row does not depend on the other gauges of the plan or on the launch.
+ *
+ * ddr_summedq_plan_create: the member lists in CSR form, host arrays (copied): gauge g's members are
+ *   member_idx[member_off[g] .. member_off[g + 1]), row indices into qr, summed in this order.  member_off starts
+ *   at 0 and does not decrease; no index is negative.  A list longer than `chunk` members (1 <= chunk <= 2^30;
+ *   4096 is a good default) is cut at multiples of `chunk` from its start into pieces summed by separate waves,
+ *   whose fp64 partial rows are added in piece order: the value depends on `chunk` (in the last fp64 bits), not
+ *   on anything else.  The device copies are made on the current device through `stream`, which is synchronised
+ *   before the call returns.  Without a HIP device the plan is still made and ddr_summedq_f32 still checks its
+ *   arguments, then fails with DDR_ERR_HIP.
+ * ddr_summedq_scratch_bytes: the bytes of fp64 partial rows ddr_summedq_f32 needs for n_days days (0 when no list
+ *   is cut); -1 for a null plan or a negative n_days.
+ * ddr_summedq_f32: one or two launches on `stream`, no allocation, no host sync (capturable).
+ *   qr      device fp32, row i at qr + i * row_stride (elements; row_stride >= n_steps, so a time slice of a
+ *           wider store is passed without a copy), n_rows > the plan's largest index.  16-byte loads are used
+ *           when qr is 16-byte aligned and row_stride a multiple of 4, 4-byte loads otherwise: same values.
+ *   out     device fp32 (n_gauges, D), row g at out + g * out_stride (out_stride >= D)
+ *   scratch device memory of at least ddr_summedq_scratch_bytes(plan, D) bytes (may be NULL when that is 0)
+ * Refused with DDR_ERR_ARG before any launch: negative sizes, hours_per_step outside {1, 24}, n_steps <
+ * hours_per_step, short strides, n_rows not above the largest index, short scratch, null pointers where data is
+ * required.  A plan of 0 gauges is a no-op. */
+typedef void* ddr_summedq_plan;
+ddr_status ddr_summedq_plan_create(int64_t n_gauges, const int64_t* member_off, const int32_t* member_idx,
+                                   int64_t chunk, void* stream, ddr_summedq_plan* plan);
+ddr_status ddr_summedq_plan_destroy(ddr_summedq_plan plan);
+int64_t ddr_summedq_scratch_bytes(ddr_summedq_plan plan, int64_t n_days);
+ddr_status ddr_summedq_f32(ddr_summedq_plan plan, const float* qr, int64_t n_rows, int64_t row_stride, int64_t n_steps,
+                           int32_t hours_per_step, float* out, int64_t out_stride, void* scratch,
+                           int64_t scratch_bytes, void* stream);
+
 /* The geometry predictor around the KAN (src/ddr/geometry/predictor.py, adapters.py): two launches that with
  * ddr_kan_forward_f32 between them take raw catchment attributes to channel geometry.  Device pointers, fp32
  * unless stated, no host sync, no allocation; n_rows == 0 is a no-op.
