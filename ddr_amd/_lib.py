@@ -146,6 +146,11 @@ _SIGS = {
     "ddr_geometry_predict_f32": (C.c_int, [_I64, _I32, _P, C.POINTER(GeomSlot), C.POINTER(GeomSlot),
                                            C.POINTER(GeomSlot), _P, _P, C.c_double, C.c_double, C.c_double,
                                            C.c_double, _P, _I64, _P]),
+    "ddr_bmi_nexus_table": (C.c_int, [_I64, _P, _P, _I64, _P, _P, _P]),
+    "ddr_bmi_nexus_plan": (C.c_int, [_I64, _P, _I64, _P, _P, _I64, _P, _P]),
+    "ddr_bmi_set_inflow_f64": (C.c_int, [_I64, _P, _I64, _P, _P, _P]),
+    "ddr_bmi_window_f32": (C.c_int, [_I64, _I32, _I32, _I32, _P, _P, _P, _I64, _P]),
+    "ddr_bmi_outputs_f32": (C.c_int, [_I64, _P, _P, _P, _P, _I64, _P, _P, _P, C.c_double, C.c_double, _P, _I64, _P]),
     "ddr_clip_adam_work_bytes": (_I64, []),
     "ddr_clip_adam_f32": (C.c_int, [_I64, _P, _P, _P, _P, C.c_float, C.c_float, C.c_float, C.c_float, _P,
                                     C.c_float, _P, _P, _P]),

@@ -16,6 +16,7 @@
 #include "kan.h"
 #include "geopredict.h"
 #include "summedq.h"
+#include "bmi.h"
 
 namespace ddr {
 
@@ -1250,6 +1251,82 @@ ddr_status ddr_geometry_predict_f32(int64_t n_rows, int32_t n_outputs, const flo
                                     const float* slope, double discharge_lb, double slope_lb, double depth_lb,
                                     double bottom_width_lb, float* out, int64_t out_stride, void* stream) {
   DDR_GUARD({ return geometry_predict_impl(n_rows, n_outputs, u, slot_n, slot_q, slot_p, discharge, slope, discharge_lb, slope_lb, depth_lb, bottom_width_lb, out, out_stride, stream); })
+}
+// ---- the BMI coupling (bmi.hip) ----
+ddr_status ddr_bmi_nexus_table(int64_t n_keys, const int64_t* keys_host, const int32_t* seg_host, int64_t n_segments,
+                               int64_t* keys, int32_t* key_seg, void* stream) {
+  DDR_GUARD({
+    if (n_keys < 0 || n_segments < 0) return fail(DDR_ERR_ARG, "bmi nexus table: negative size");
+    if (n_segments > INT32_MAX) return fail(DDR_ERR_ARG, "bmi nexus table: more segments than int32 indices");
+    if (n_keys == 0) return DDR_OK;
+    if (!keys_host || !seg_host || !keys || !key_seg) return fail(DDR_ERR_ARG, "bmi nexus table: null argument");
+    for (int64_t j = 0; j < n_keys; ++j) {
+      if (j > 0 && keys_host[j] <= keys_host[j - 1])
+        return fail(DDR_ERR_ARG, "bmi nexus table: keys must be strictly ascending (key " + std::to_string(j) + ")");
+      if (seg_host[j] < 0 || seg_host[j] >= n_segments)
+        return fail(DDR_ERR_ARG, "bmi nexus table: segment index " + std::to_string(seg_host[j]) + " of key " +
+                                     std::to_string(j) + " is outside [0, " + std::to_string(n_segments) + ")");
+    }
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    DDR_HIP(hipMemcpyAsync(keys, keys_host, sizeof(int64_t) * (size_t)n_keys, hipMemcpyHostToDevice, s));
+    DDR_HIP(hipMemcpyAsync(key_seg, seg_host, sizeof(int32_t) * (size_t)n_keys, hipMemcpyHostToDevice, s));
+    DDR_HIP(hipStreamSynchronize(s));  // (the host arrays are the caller's again on return)
+    return DDR_OK;
+  })
+}
+ddr_status ddr_bmi_nexus_plan(int64_t n_ids, const int32_t* ids, int64_t n_keys, const int64_t* keys,
+                              const int32_t* key_seg, int64_t n_segments, int32_t* src_of_seg, void* stream) {
+  DDR_GUARD({
+    if (n_ids < 0 || n_keys < 0 || n_segments < 0) return fail(DDR_ERR_ARG, "bmi nexus plan: negative size");
+    if (n_ids > INT32_MAX || n_segments > INT32_MAX)
+      return fail(DDR_ERR_ARG, "bmi nexus plan: more ids or segments than int32 indices");
+    if ((n_segments > 0 && !src_of_seg) || (n_ids > 0 && !ids) || (n_keys > 0 && (!keys || !key_seg)))
+      return fail(DDR_ERR_ARG, "bmi nexus plan: null argument");
+    DDR_HIP(launch_bmi_nexus_plan(n_ids, ids, n_keys, keys, key_seg, n_segments, src_of_seg,
+                                  static_cast<hipStream_t>(stream)));
+    return DDR_OK;
+  })
+}
+ddr_status ddr_bmi_set_inflow_f64(int64_t n_segments, const int32_t* src, int64_t n_flows, const double* flows,
+                                  double* lateral, void* stream) {
+  DDR_GUARD({
+    if (n_segments < 0 || n_flows < 0) return fail(DDR_ERR_ARG, "bmi set inflow: negative size");
+    if (n_segments > 0 && n_flows > 0 && (!src || !flows || !lateral))
+      return fail(DDR_ERR_ARG, "bmi set inflow: null argument");
+    DDR_HIP(launch_bmi_set_inflow(n_segments, src, n_flows, flows, lateral, static_cast<hipStream_t>(stream)));
+    return DDR_OK;
+  })
+}
+ddr_status ddr_bmi_window_f32(int64_t n_segments, int32_t n_rows, int32_t n_steps, int32_t linear, double* prev,
+                              double* cur, float* window, int64_t row_stride, void* stream) {
+  DDR_GUARD({
+    if (n_segments < 0) return fail(DDR_ERR_ARG, "bmi window: negative size");
+    if (n_rows < 1 || n_steps < n_rows)
+      return fail(DDR_ERR_ARG, "bmi window: need 1 <= n_rows <= n_steps (got " + std::to_string(n_rows) + ", " +
+                                   std::to_string(n_steps) + ")");
+    if (row_stride < n_segments) return fail(DDR_ERR_ARG, "bmi window: row_stride is shorter than a row");
+    if (n_segments > 0 && (!prev || !cur || !window)) return fail(DDR_ERR_ARG, "bmi window: null argument");
+    DDR_HIP(launch_bmi_window(n_segments, n_rows, n_steps, linear != 0, prev, cur, window, row_stride,
+                              static_cast<hipStream_t>(stream)));
+    return DDR_OK;
+  })
+}
+ddr_status ddr_bmi_outputs_f32(int64_t n_segments, const float* discharge, const float* n_manning,
+                               const float* q_spatial, const float* p_spatial, int64_t p_stride, const float* slope,
+                               const float* top_width, const float* side_slope, double depth_lb,
+                               double bottom_width_lb, float* out, int64_t out_stride, void* stream) {
+  DDR_GUARD({
+    if (n_segments < 0) return fail(DDR_ERR_ARG, "bmi outputs: negative size");
+    if (p_stride != 0 && p_stride != 1) return fail(DDR_ERR_ARG, "bmi outputs: p_stride must be 0 or 1");
+    if (out_stride < n_segments) return fail(DDR_ERR_ARG, "bmi outputs: out_stride is shorter than a row");
+    if (n_segments > 0 &&
+        (!discharge || !n_manning || !q_spatial || !p_spatial || !slope || !top_width || !side_slope || !out))
+      return fail(DDR_ERR_ARG, "bmi outputs: null argument");
+    DDR_HIP(launch_bmi_outputs(n_segments, discharge, n_manning, q_spatial, p_spatial, p_stride, slope, top_width,
+                               side_slope, (float)depth_lb, (float)bottom_width_lb, out, out_stride,
+                               static_cast<hipStream_t>(stream)));
+    return DDR_OK;
+  })
 }
 int64_t ddr_clip_adam_work_bytes(void) { return (int64_t)clip_adam_work_bytes(); }
 ddr_status ddr_clip_adam_f32(int64_t n, float* params, const float* grad, float* m, float* v, float lr, float beta1,

@@ -597,6 +597,45 @@ ddr_status ddr_geometry_predict_f32(int64_t n_rows, int32_t n_outputs, const flo
                                     const float* slope, double discharge_lb, double slope_lb, double depth_lb,
                                     double bottom_width_lb, float* out, int64_t out_stride, void* stream);
 
+/* ---- The BMI coupling's device side (the reference's src/ddr/bmi/ddr_bmi.py; bmi.hip) ------------------------
+ * Stateless: the caller (ddr_amd.bmi.DdrBmi) owns every array.  All pointers are device pointers unless named
+ * *_host; every call is queued on `stream` and returns without a host sync except ddr_bmi_nexus_table.
+ * Arguments are checked before anything is launched (DDR_ERR_ARG and a message).
+ *
+ * ddr_bmi_nexus_table  the nexus -> segment dictionary as two device arrays: checks on the host that keys_host
+ *           is strictly ascending and every seg_host is in [0, n_segments), then copies both to keys / key_seg
+ *           (n_keys elements each) and waits for the copies.
+ * ddr_bmi_nexus_plan   set_value("land_surface_water_source__id") (ddr_bmi.py:432-433 and the loop of 424-427):
+ *           src_of_seg (n_segments) is set to -1, then src_of_seg[key_seg[j]] = the LAST i with ids[i] == keys[j]
+ *           (the reference's sequential loop: a repeated id, or two ids of one segment, leave the last value);
+ *           ids absent from the table are skipped.
+ * ddr_bmi_set_inflow_f64  lateral[s] = flows[src[s]] where 0 <= src[s] < n_flows; the other segments keep their
+ *           value (ddr_bmi.py:427; with a host-built src also set_value_at_indices, 443-445).
+ * ddr_bmi_window_f32   update_until's inflows (ddr_bmi.py:270-281, 313-318) for the n_rows sub-steps the call
+ *           executes out of the n_steps it planned: window row k (k < n_rows, rows of row_stride floats) =
+ *           (float)((1.0 - a) * prev + a * cur), a = (double)(k + 1) / n_steps, in separately rounded fp64
+ *           (linear != 0), or (float)cur; row n_rows repeats row n_rows - 1 (the routing kernel's step t reads
+ *           row t - 1, so a window of n_rows + 1 rows is n_rows steps).  Then prev = cur and cur = 0.  Nothing is
+ *           clamped: the routing kernel clamps its steps and its hot start reads row 0 raw (ddr_bmi.py:284-297).
+ * ddr_bmi_outputs_f32  _update_output_cache (ddr_bmi.py:587-630) in its fp32 operation order with IEEE division
+ *           and square root and the correctly rounded pow: out row 0 = discharge, row 1 = velocity clamped to
+ *           [0, 15], row 2 = depth clamped from below by depth_lb (rows of out_stride floats).  top_width /
+ *           side_slope are the routing engine's; p_spatial is one value (p_stride = 0) or per segment (1).
+ * Replaces, per coupling interval: a Python loop over every nexus id, n_rows host interpolations and uploads,
+ * ~25 element-wise launches and three device-to-host copies. */
+ddr_status ddr_bmi_nexus_table(int64_t n_keys, const int64_t* keys_host, const int32_t* seg_host, int64_t n_segments,
+                               int64_t* keys, int32_t* key_seg, void* stream);
+ddr_status ddr_bmi_nexus_plan(int64_t n_ids, const int32_t* ids, int64_t n_keys, const int64_t* keys,
+                              const int32_t* key_seg, int64_t n_segments, int32_t* src_of_seg, void* stream);
+ddr_status ddr_bmi_set_inflow_f64(int64_t n_segments, const int32_t* src, int64_t n_flows, const double* flows,
+                                  double* lateral, void* stream);
+ddr_status ddr_bmi_window_f32(int64_t n_segments, int32_t n_rows, int32_t n_steps, int32_t linear, double* prev,
+                              double* cur, float* window, int64_t row_stride, void* stream);
+ddr_status ddr_bmi_outputs_f32(int64_t n_segments, const float* discharge, const float* n_manning,
+                               const float* q_spatial, const float* p_spatial, int64_t p_stride, const float* slope,
+                               const float* top_width, const float* side_slope, double depth_lb,
+                               double bottom_width_lb, float* out, int64_t out_stride, void* stream);
+
 /* Synchronise `stream` and read the device status block written by the last launches:
  * returns DDR_OK or DDR_ERR_TIMEOUT. */
 ddr_status ddr_graph_status(const void* status, void* stream);
