@@ -32,6 +32,9 @@ DDR_ERR_SINGULAR = -8
 
 DDR_BUILD_HOST_ONLY = 1
 
+DDR_UPSTREAM_HOST_ONLY = 1
+DDR_UPSTREAM_DEVICE_COO = 2
+
 DDR_FWD_SAVE_X = 1
 DDR_FWD_CARRY = 2
 DDR_FWD_NO_RUNOFF = 4
@@ -78,6 +81,10 @@ class Gauges(C.Structure):
 
 class KanDesc(C.Structure):
     _fields_ = [(name, C.c_int32) for name in ("n_features", "hidden", "n_outputs", "n_layers", "grid", "k")]
+
+
+class UpstreamInfo(C.Structure):
+    _fields_ = [(name, C.c_int64) for name in ("n", "n_outlets", "max_depth", "rounds", "device")]
 
 
 class GeomSlot(C.Structure):
@@ -142,6 +149,21 @@ _SIGS = {
     "ddr_summedq_plan_destroy": (C.c_int, [_P]),
     "ddr_summedq_scratch_bytes": (_I64, [_P, _I64]),
     "ddr_summedq_f32": (C.c_int, [_P, _P, _I64, _I64, _I64, _I32, _P, _I64, _P, _I64, _P]),
+    "ddr_upstream_index_create": (C.c_int, [_I64, _I64, _P, _P, _I32, _P, C.POINTER(C.c_void_p)]),
+    "ddr_upstream_index_destroy": (C.c_int, [_P]),
+    "ddr_upstream_index_info": (C.c_int, [_P, C.POINTER(UpstreamInfo)]),
+    "ddr_upstream_index_down": (C.c_int, [_P, _P]),
+    "ddr_upstream_scratch_bytes": (_I64, [_P, _I64, _I64]),
+    "ddr_upstream_label": (C.c_int, [_P, _I64, _P, _P, _P, _P, _I64, _P]),
+    "ddr_upstream_collate": (C.c_int, [_P, _I64, _P, _P, _I64, C.POINTER(C.c_int64), _P, _P, _I64,
+                                       C.POINTER(C.c_int64), _P, _P, _P, _P, _I64, _P, _P, _I64, _P]),
+    "ddr_upstream_member_counts": (C.c_int, [_P, _I64, _P, _P, C.POINTER(C.c_int64), _P, _I64, _P]),
+    "ddr_upstream_members": (C.c_int, [_P, _I64, _P, _I64, _P, _P, _I64, _P]),
+    "ddr_upstream_label_host": (C.c_int, [_P, _I64, _P, _P, _P]),
+    "ddr_upstream_collate_host": (C.c_int, [_P, _I64, _P, _P, _I64, C.POINTER(C.c_int64), _P, _P, _I64,
+                                            C.POINTER(C.c_int64), _P, _P, _I64, _P]),
+    "ddr_upstream_member_counts_host": (C.c_int, [_P, _I64, _P, _P]),
+    "ddr_upstream_members_host": (C.c_int, [_P, _I64, _P, _P, _P]),
     "ddr_attr_prepare_f32": (C.c_int, [_I64, _I32, _P, _I64, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "ddr_geometry_predict_f32": (C.c_int, [_I64, _I32, _P, C.POINTER(GeomSlot), C.POINTER(GeomSlot),
                                            C.POINTER(GeomSlot), _P, _P, C.c_double, C.c_double, C.c_double,

@@ -17,6 +17,7 @@
 #include "geopredict.h"
 #include "summedq.h"
 #include "bmi.h"
+#include "upstream.h"
 
 namespace ddr {
 
@@ -1239,6 +1240,91 @@ ddr_status ddr_summedq_f32(ddr_summedq_plan plan, const float* qr, int64_t n_row
     return summedq_run(static_cast<const SummedQPlan*>(plan), qr, n_rows, row_stride, n_steps, hours_per_step, out,
                        out_stride, scratch, scratch_bytes, static_cast<hipStream_t>(stream));
   })
+}
+ddr_status ddr_upstream_index_create(int64_t n, int64_t e, const int32_t* rows, const int32_t* cols, int32_t flags,
+                                     void* stream, ddr_upstream_index* index) {
+  DDR_GUARD({
+    return upstream_index_create(n, e, rows, cols, flags, static_cast<hipStream_t>(stream),
+                                 reinterpret_cast<UpstreamIndex**>(index));
+  })
+}
+ddr_status ddr_upstream_index_destroy(ddr_upstream_index index) {
+  upstream_index_destroy(static_cast<UpstreamIndex*>(index));
+  return DDR_OK;
+}
+ddr_status ddr_upstream_index_info(ddr_upstream_index index, ddr_upstream_info* info) {
+  if (!index || !info) return fail(DDR_ERR_ARG, "upstream_index_info: null argument");
+  const auto* ix = static_cast<const UpstreamIndex*>(index);
+  info->n = ix->n;
+  info->n_outlets = ix->n_outlets;
+  info->max_depth = ix->max_depth;
+  info->rounds = ix->rounds;
+  info->device = ix->device;
+  return DDR_OK;
+}
+ddr_status ddr_upstream_index_down(ddr_upstream_index index, int32_t* down) {
+  if (!index || !down) return fail(DDR_ERR_ARG, "upstream_index_down: null argument");
+  const auto* ix = static_cast<const UpstreamIndex*>(index);
+  std::copy(ix->down.begin(), ix->down.end(), down);
+  return DDR_OK;
+}
+int64_t ddr_upstream_scratch_bytes(ddr_upstream_index index, int64_t n_targets, int64_t n_members) {
+  return upstream_scratch_bytes(static_cast<const UpstreamIndex*>(index), n_targets, n_members);
+}
+ddr_status ddr_upstream_label(ddr_upstream_index index, int64_t n_targets, const int32_t* targets, int32_t* label_out,
+                              int32_t* slot_of, void* scratch, int64_t scratch_bytes, void* stream) {
+  DDR_GUARD({
+    return upstream_label(static_cast<const UpstreamIndex*>(index), n_targets, targets, label_out, slot_of, scratch,
+                          scratch_bytes, static_cast<hipStream_t>(stream));
+  })
+}
+ddr_status ddr_upstream_collate(ddr_upstream_index index, int64_t n_gauges, const int32_t* gage_idx, int32_t* active,
+                                int64_t active_cap, int64_t* n_active, int32_t* rows_c, int32_t* cols_c,
+                                int64_t edge_cap, int64_t* nnz, int64_t* crow, int32_t* col, int64_t* out_off,
+                                int32_t* out_idx, int64_t out_idx_cap, int32_t* gage_c, void* scratch,
+                                int64_t scratch_bytes, void* stream) {
+  DDR_GUARD({
+    return upstream_collate(static_cast<const UpstreamIndex*>(index), n_gauges, gage_idx, active, active_cap, n_active,
+                            rows_c, cols_c, edge_cap, nnz, crow, col, out_off, out_idx, out_idx_cap, gage_c, scratch,
+                            scratch_bytes, static_cast<hipStream_t>(stream));
+  })
+}
+ddr_status ddr_upstream_member_counts(ddr_upstream_index index, int64_t n_gauges, const int32_t* gage_idx, int64_t* off,
+                                      int64_t* total, void* scratch, int64_t scratch_bytes, void* stream) {
+  DDR_GUARD({
+    return upstream_member_counts(static_cast<const UpstreamIndex*>(index), n_gauges, gage_idx, off, total, scratch,
+                                  scratch_bytes, static_cast<hipStream_t>(stream));
+  })
+}
+ddr_status ddr_upstream_members(ddr_upstream_index index, int64_t n_gauges, const int32_t* gage_idx, int64_t n_members,
+                                int32_t* idx, void* scratch, int64_t scratch_bytes, void* stream) {
+  DDR_GUARD({
+    return upstream_members(static_cast<const UpstreamIndex*>(index), n_gauges, gage_idx, n_members, idx, scratch,
+                            scratch_bytes, static_cast<hipStream_t>(stream));
+  })
+}
+ddr_status ddr_upstream_label_host(ddr_upstream_index index, int64_t n_targets, const int32_t* targets,
+                                   int32_t* label_out, int32_t* slot_of) {
+  DDR_GUARD({
+    return upstream_label_host(static_cast<const UpstreamIndex*>(index), n_targets, targets, label_out, slot_of);
+  })
+}
+ddr_status ddr_upstream_collate_host(ddr_upstream_index index, int64_t n_gauges, const int32_t* gage_idx,
+                                     int32_t* active, int64_t active_cap, int64_t* n_active, int64_t* crow,
+                                     int32_t* col, int64_t edge_cap, int64_t* nnz, int64_t* out_off, int32_t* out_idx,
+                                     int64_t out_idx_cap, int32_t* gage_c) {
+  DDR_GUARD({
+    return upstream_collate_host(static_cast<const UpstreamIndex*>(index), n_gauges, gage_idx, active, active_cap,
+                                 n_active, crow, col, edge_cap, nnz, out_off, out_idx, out_idx_cap, gage_c);
+  })
+}
+ddr_status ddr_upstream_member_counts_host(ddr_upstream_index index, int64_t n_gauges, const int32_t* gage_idx,
+                                           int64_t* off) {
+  DDR_GUARD({ return upstream_member_counts_host(static_cast<const UpstreamIndex*>(index), n_gauges, gage_idx, off); })
+}
+ddr_status ddr_upstream_members_host(ddr_upstream_index index, int64_t n_gauges, const int32_t* gage_idx,
+                                     const int64_t* off, int32_t* idx) {
+  DDR_GUARD({ return upstream_members_host(static_cast<const UpstreamIndex*>(index), n_gauges, gage_idx, off, idx); })
 }
 ddr_status ddr_attr_prepare_f32(int64_t n_rows, int32_t n_features, const float* raw, int64_t feat_stride,
                                 const double* scale, const double* offset, const int32_t* log10_flag,

@@ -530,6 +530,77 @@ ddr_status ddr_summedq_f32(ddr_summedq_plan plan, const float* qr, int64_t n_row
                            int32_t hours_per_step, float* out, int64_t out_stride, void* scratch,
                            int64_t scratch_bytes, void* stream);
 
+/* The upstream index: everything upstream of a set of reaches, from the network's COO alone.  It replaces the
+ * per-gauge rx.ancestors of the reference (engine/src/ddr_engine/merit/build.py:206-290 build_gauge_adjacencies,
+ * graph.py:89-115 subset_upstream; src/ddr/geodatazoo/merit.py:321-396 _build_routing_data_target_catchments; the
+ * membership step of scripts/summed_q_prime.py).  The network is the conus_adjacency contract: strictly lower
+ * triangular COO (row = downstream reach), dendritic.
+ *
+ * ddr_upstream_index_create: builds down[n] (-1: outlet), the outlet count and max_depth, the longest
+ *   reach-to-outlet path in edges.  rows/cols are host arrays, or with DDR_UPSTREAM_DEVICE_COO device arrays on the
+ *   current device (down[] and the depths are then computed on the device).  DDR_UPSTREAM_HOST_ONLY builds an index
+ *   that needs no device and serves the _host queries alone; any other index lives on the current device and serves
+ *   both.  `stream` is synchronised before the call returns.  n >= 1; e == 0 is valid (every reach isolated).
+ *   Refused: rows[k] <= cols[k] (DDR_ERR_NOT_LOWER), a reach with two different downstream reaches
+ *   (DDR_ERR_NOT_DENDRITIC), an index out of range (DDR_ERR_ARG).  The same edge given twice is accepted.
+ * ddr_upstream_index_info: rounds = 0 without edges, else ceil(log2(max_depth)) + 1, the doubling rounds of every
+ *   device query (fixed by the index, so no query reads the device to know when to stop); device = -1: host-only.
+ * ddr_upstream_index_down: down[n] copied to a host array.
+ *
+ * Queries.  `targets` / `gage_idx` are always HOST arrays of reach indices in [0, n) (checked before anything is
+ * launched, then uploaded); several may name one reach: slot_of[g] is the smallest slot on g's reach, the others are
+ * its aliases.  Every other array of a device query is device memory, of a _host query host memory.  Device queries
+ * take `scratch` of at least ddr_upstream_scratch_bytes(index, n_targets, n_members) bytes (n_members = 0 except for
+ * ddr_upstream_members) and allocate nothing themselves, apart from the pooled blocks of the union inside
+ * ddr_upstream_collate.
+ *
+ * ddr_upstream_label: label_out[i] (int32[n]) = the slot of the nearest target at or downstream of reach i, -1
+ *   without one; label >= 0 is the closure mask.  slot_of (host int32[n_targets], may be NULL).  Pointer doubling,
+ *   one launch per round; the target upload is waited for, nothing is read back.
+ * ddr_upstream_collate: the union subnetwork of the gauges' closures; the outputs are those of
+ *   ddr_collate_gauges_device (bit-identical to collating the gauges' complete upstream subsets) with explicit
+ *   capacities: active[active_cap], rows_c/cols_c/col[edge_cap] (n always suffices), out_idx[out_idx_cap].  A gauge
+ *   whose reach has nothing upstream appears as itself.  Synchronous.
+ * ddr_upstream_member_counts / ddr_upstream_members: off (int64[n_gauges + 1]) and idx (int32[n_members], n_members
+ *   = *total = off[n_gauges]): gauge g's reach and everything upstream of it, ascending, at idx[off[g] .. off[g+1]).
+ *   Nested gauges repeat their shared reaches; aliases get equal lists.  A total of 2^31 or more is refused.
+ *   Synchronous.  The _host twin of ddr_upstream_members takes the off of ddr_upstream_member_counts_host.
+ *
+ * Refused with DDR_ERR_ARG and a message naming the fault, before any launch: null pointers, negative counts, a
+ * target outside [0, n), scratch too small, a host-only index given to a device query. */
+typedef void* ddr_upstream_index;
+enum { DDR_UPSTREAM_HOST_ONLY = 1, DDR_UPSTREAM_DEVICE_COO = 2 };
+typedef struct {
+  int64_t n, n_outlets, max_depth, rounds, device;
+} ddr_upstream_info;
+ddr_status ddr_upstream_index_create(int64_t n, int64_t e, const int32_t* rows, const int32_t* cols, int32_t flags,
+                                     void* stream, ddr_upstream_index* index);
+ddr_status ddr_upstream_index_destroy(ddr_upstream_index index);
+ddr_status ddr_upstream_index_info(ddr_upstream_index index, ddr_upstream_info* info);
+ddr_status ddr_upstream_index_down(ddr_upstream_index index, int32_t* down);
+int64_t ddr_upstream_scratch_bytes(ddr_upstream_index index, int64_t n_targets, int64_t n_members);
+ddr_status ddr_upstream_label(ddr_upstream_index index, int64_t n_targets, const int32_t* targets, int32_t* label_out,
+                              int32_t* slot_of, void* scratch, int64_t scratch_bytes, void* stream);
+ddr_status ddr_upstream_collate(ddr_upstream_index index, int64_t n_gauges, const int32_t* gage_idx, int32_t* active,
+                                int64_t active_cap, int64_t* n_active, int32_t* rows_c, int32_t* cols_c,
+                                int64_t edge_cap, int64_t* nnz, int64_t* crow, int32_t* col, int64_t* out_off,
+                                int32_t* out_idx, int64_t out_idx_cap, int32_t* gage_c, void* scratch,
+                                int64_t scratch_bytes, void* stream);
+ddr_status ddr_upstream_member_counts(ddr_upstream_index index, int64_t n_gauges, const int32_t* gage_idx, int64_t* off,
+                                      int64_t* total, void* scratch, int64_t scratch_bytes, void* stream);
+ddr_status ddr_upstream_members(ddr_upstream_index index, int64_t n_gauges, const int32_t* gage_idx, int64_t n_members,
+                                int32_t* idx, void* scratch, int64_t scratch_bytes, void* stream);
+ddr_status ddr_upstream_label_host(ddr_upstream_index index, int64_t n_targets, const int32_t* targets,
+                                   int32_t* label_out, int32_t* slot_of);
+ddr_status ddr_upstream_collate_host(ddr_upstream_index index, int64_t n_gauges, const int32_t* gage_idx,
+                                     int32_t* active, int64_t active_cap, int64_t* n_active, int64_t* crow,
+                                     int32_t* col, int64_t edge_cap, int64_t* nnz, int64_t* out_off, int32_t* out_idx,
+                                     int64_t out_idx_cap, int32_t* gage_c);
+ddr_status ddr_upstream_member_counts_host(ddr_upstream_index index, int64_t n_gauges, const int32_t* gage_idx,
+                                           int64_t* off);
+ddr_status ddr_upstream_members_host(ddr_upstream_index index, int64_t n_gauges, const int32_t* gage_idx,
+                                     const int64_t* off, int32_t* idx);
+
 /* The geometry predictor around the KAN (src/ddr/geometry/predictor.py, adapters.py): two launches that with
  * ddr_kan_forward_f32 between them take raw catchment attributes to channel geometry.  Device pointers, fp32
  * unless stated, no host sync, no allocation; n_rows == 0 is a no-op.
