@@ -31,7 +31,7 @@ def consts_of(case):
 
 
 def run_hip(case, dev, dtype=torch.float32, gkw=None, gauges=None, q0=None, qprime=None, W=None, grads=True,
-            graph=None, math="exact"):
+            graph=None, math="exact", exact_adjoint=False, qprime_grad=False):
     """Reference recipe on the device: denormalize in torch, fused route, backward(W)."""
     rng = case.params["parameter_ranges"]
     ls = case.params["log_space_parameters"]
@@ -43,9 +43,10 @@ def run_hip(case, dev, dtype=torch.float32, gkw=None, gauges=None, q0=None, qpri
          else torch.tensor(float(case.params["defaults"]["p_spatial"]), device=dev, dtype=dtype))
     slope = torch.clamp(tt(case.slope), min=case.params["attribute_minimums"]["slope"])
     g = graph if graph is not None else RiverGraph(case.n, case.rows, case.cols, **(gkw or {}))
-    qp = tt(case.qprime if qprime is None else qprime)
+    qp = tt(case.qprime if qprime is None else qprime).requires_grad_(qprime_grad)
     runoff, q_last, tw, ss = route(g, qp, n, q, p, tt(case.length), slope, tt(case.x), gauges=gauges,
-                                   q0=None if q0 is None else tt(q0), consts=consts_of(case), math=math)
+                                   q0=None if q0 is None else tt(q0), consts=consts_of(case), math=math,
+                                   exact_adjoint=exact_adjoint)
     out = {"runoff": runoff.detach().cpu().numpy(), "q_last": q_last.detach().cpu().numpy(),
            "top_width": tw.detach().cpu().numpy(), "side_slope": ss.detach().cpu().numpy(), "graph": g}
     # the exact physical inputs the kernel saw (torch's device expf in the log-space denormalize may
@@ -59,6 +60,8 @@ def run_hip(case, dev, dtype=torch.float32, gkw=None, gauges=None, q0=None, qpri
         for k, v in u.items():
             if v is not None:
                 out[f"grad_{k}"] = v.grad.detach().cpu().numpy()
+        if qprime_grad:
+            out["grad_qprime"] = qp.grad.detach().cpu().numpy()
     torch.cuda.synchronize()
     return out
 
