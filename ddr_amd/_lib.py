@@ -149,6 +149,8 @@ _SIGS = {
     "ddr_summedq_plan_destroy": (C.c_int, [_P]),
     "ddr_summedq_scratch_bytes": (_I64, [_P, _I64]),
     "ddr_summedq_f32": (C.c_int, [_P, _P, _I64, _I64, _I64, _I32, _P, _I64, _P, _I64, _P]),
+    "ddr_feed_qprime_f32": (C.c_int, [_P, _I64, _I64, _I64, _P, _I64, _I64, _I64, _I32, _I64, C.c_float, _P, _P, _P]),
+    "ddr_feed_rows_f32": (C.c_int, [_P, _I64, _I64, _I64, _P, _I64, _I64, _I64, _I32, _P, _I64, _P, _P]),
     "ddr_upstream_index_create": (C.c_int, [_I64, _I64, _P, _P, _I32, _P, C.POINTER(C.c_void_p)]),
     "ddr_upstream_index_destroy": (C.c_int, [_P]),
     "ddr_upstream_index_info": (C.c_int, [_P, C.POINTER(UpstreamInfo)]),

@@ -18,6 +18,7 @@
 #include "summedq.h"
 #include "bmi.h"
 #include "upstream.h"
+#include "feed.h"
 
 namespace ddr {
 
@@ -1239,6 +1240,22 @@ ddr_status ddr_summedq_f32(ddr_summedq_plan plan, const float* qr, int64_t n_row
   DDR_GUARD({
     return summedq_run(static_cast<const SummedQPlan*>(plan), qr, n_rows, row_stride, n_steps, hours_per_step, out,
                        out_stride, scratch, scratch_bytes, static_cast<hipStream_t>(stream));
+  })
+}
+ddr_status ddr_feed_qprime_f32(const float* store, int64_t row_stride, int64_t n_rows, int64_t n_store_cols,
+                               const int32_t* rows, int64_t n_reaches, int64_t t0, int64_t n_cols, int32_t repeat,
+                               int64_t n_out, float fill, float* out, uint8_t* valid, void* stream) {
+  DDR_GUARD({
+    return feed_qprime(store, row_stride, n_rows, n_store_cols, rows, n_reaches, t0, n_cols, repeat, n_out, fill, out,
+                       valid, static_cast<hipStream_t>(stream));
+  })
+}
+ddr_status ddr_feed_rows_f32(const float* store, int64_t row_stride, int64_t n_rows, int64_t n_store_cols,
+                             const int32_t* rows, int64_t n_out_rows, int64_t t0, int64_t n_cols, int32_t trim,
+                             float* out, int64_t out_stride, uint8_t* has_nan, void* stream) {
+  DDR_GUARD({
+    return feed_rows(store, row_stride, n_rows, n_store_cols, rows, n_out_rows, t0, n_cols, trim, out, out_stride,
+                     has_nan, static_cast<hipStream_t>(stream));
   })
 }
 ddr_status ddr_upstream_index_create(int64_t n, int64_t e, const int32_t* rows, const int32_t* cols, int32_t flags,

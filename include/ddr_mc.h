@@ -530,6 +530,36 @@ ddr_status ddr_summedq_f32(ddr_summedq_plan plan, const float* qr, int64_t n_row
                            int32_t hours_per_step, float* out, int64_t out_stride, void* scratch,
                            int64_t scratch_bytes, void* stream);
 
+/* The per-batch forcing feed: the batch's lateral inflow and observations gathered on the device from stores that
+ * were uploaded once, in place of the reference's per-batch host readers (src/ddr/io/readers.py:461-531
+ * StreamflowReader.forward; io/builders.py:112-129 with scripts/train.py:84-92 for the observations).
+ * Both stores are device fp32 with time on the inner axis, row i at store + i * row_stride (elements; row_stride >=
+ * n_store_cols, so a time slice or a view of a wider buffer is passed without a copy); `rows` is device int32, the
+ * store row of every output reach / gauge, where any value outside [0, n_rows) means "the store lacks it" and is
+ * never used as an address.  Values are copied as bits (NaN payloads, -0.0).  One launch each on `stream`, no
+ * allocation, no host sync (capturable), no atomics.
+ *
+ * ddr_feed_qprime_f32: out (n_out, n_reaches) with reaches on the inner axis, the layout ddr_mc_forward reads:
+ *     out[t][i] = store[rows[i]][t0 + t / repeat]        rows[i] in the store          valid[i] = 1
+ *     out[t][i] = fill                                   otherwise (readers.py:523-530) valid[i] = 0
+ *   repeat = 1 copies n_cols = n_out columns (an hourly store, or a daily store for qprime_hours = 24); repeat = 24
+ *   expands a daily store to hours (readers.py:513-519); n_cols = ceil(n_out / repeat), the last column repeated
+ *   only up to n_out.  16-byte loads are used when `store` is 16-byte aligned and row_stride a multiple of 4
+ *   (whatever t0), 4-byte loads otherwise: same values.  valid is device uint8 (n_reaches).
+ * ddr_feed_rows_f32: out (n_out_rows, n_cols - 2 * trim), row g at out + g * out_stride:
+ *     out[g][j]  = store[rows[g]][t0 + trim + j]           (NaN throughout for a gauge the store lacks)
+ *     has_nan[g] = 1 when any of the n_cols columns of the window is NaN, the trimmed ones included, or the gauge is
+ *                  unknown (train.py:84-87); device uint8 (n_out_rows).  trim = 1 is the training loop's [:, 1:-1].
+ * Refused with DDR_ERR_ARG before any launch: negative sizes, row_stride < n_store_cols, a window outside
+ * [0, n_store_cols], repeat < 1, n_cols != ceil(n_out / repeat), n_cols < 2 * trim, a short out_stride, null
+ * pointers where data is required.  Zero reaches / rows is a no-op. */
+ddr_status ddr_feed_qprime_f32(const float* store, int64_t row_stride, int64_t n_rows, int64_t n_store_cols,
+                               const int32_t* rows, int64_t n_reaches, int64_t t0, int64_t n_cols, int32_t repeat,
+                               int64_t n_out, float fill, float* out, uint8_t* valid, void* stream);
+ddr_status ddr_feed_rows_f32(const float* store, int64_t row_stride, int64_t n_rows, int64_t n_store_cols,
+                             const int32_t* rows, int64_t n_out_rows, int64_t t0, int64_t n_cols, int32_t trim,
+                             float* out, int64_t out_stride, uint8_t* has_nan, void* stream);
+
 /* The upstream index: everything upstream of a set of reaches, from the network's COO alone.  It replaces the
  * per-gauge rx.ancestors of the reference (engine/src/ddr_engine/merit/build.py:206-290 build_gauge_adjacencies,
  * graph.py:89-115 subset_upstream; src/ddr/geodatazoo/merit.py:321-396 _build_routing_data_target_catchments; the
