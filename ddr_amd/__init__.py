@@ -21,4 +21,8 @@ def __getattr__(name):
         from .routing.mmc import MuskingumCunge
 
         return MuskingumCunge
+    if name in ("PeriodRouter", "PeriodResult", "period_chunks"):
+        from . import inference
+
+        return getattr(inference, name)
     raise AttributeError(name)

@@ -43,6 +43,7 @@ DDR_FWD_FAST_MATH = 16
 DDR_FWD_FAITHFUL_MATH = 32
 DDR_FWD_CHECK_QPRIME = 64
 DDR_BWD_EXACT_ADJOINT = 128
+DDR_PERIOD_DIRECT_STORE = 1 << 24  # ddr_period_daily_*: the per-thread store variant (A/B timing)
 
 DDR_DEBUG_FORCE_TIMEOUT = 1
 DDR_DEBUG_NO_STEADY = 2
@@ -186,6 +187,8 @@ _SIGS = {
     "ddr_gauge_daily_f64": (C.c_int, [_P, _P, _I64, C.POINTER(Gauges), C.c_double, _I32, _I64, _I64, _I64, _P, _P]),
     "ddr_gauge_daily_seed_f32": (C.c_int, [_I64, _I64, _I64, _I64, _I64, _P, _P, _P]),
     "ddr_gauge_daily_seed_f64": (C.c_int, [_I64, _I64, _I64, _I64, _I64, _P, _P, _P]),
+    "ddr_period_daily_f32": (C.c_int, [_P, _P, _I64, C.POINTER(Gauges), C.c_double, _I32, _I64, _I64, _I64, _P, _P]),
+    "ddr_period_daily_f64": (C.c_int, [_P, _P, _I64, C.POINTER(Gauges), C.c_double, _I32, _I64, _I64, _I64, _P, _P]),
     "ddr_geometry_stats_f32": (C.c_int, [_P, _I64, _I64, _I64, _I64, _P, _P, _I64, _P, _P, C.c_double, C.c_double,
                                          _P, _P]),
     "ddr_graph_status": (C.c_int, [_P, _P]),

@@ -19,6 +19,7 @@
 #include "bmi.h"
 #include "upstream.h"
 #include "feed.h"
+#include "period.h"
 
 namespace ddr {
 
@@ -517,6 +518,43 @@ ddr_status gauge_daily_seed_impl(int64_t G, int64_t T, int64_t t0, int64_t L, in
   if (st) return st;
   if (G < 0 || (G > 0 && (!gd || !gh))) return fail(DDR_ERR_ARG, "bad daily seed arguments");
   DDR_HIP(launch_gauge_daily_seed<R>(G, T, t0, L, D, gd, gh, static_cast<hipStream_t>(stream)));
+  return DDR_OK;
+}
+
+// One routing launch's share of a period's daily series (period.hip).  gz == nullptr: every reach.
+template <typename R>
+ddr_status period_daily_impl(const ddr_graph* gh, const R* x_save, int64_t T, const ddr_gauges* gz, double qlb,
+                             int32_t flags, int64_t h0, int64_t first_hour, int64_t n_days, R* out, void* stream) {
+  if (!gh) return fail(DDR_ERR_ARG, "period daily: null graph");
+  if (!x_save) return fail(DDR_ERR_ARG, "period daily: null x_save");
+  if (!out) return fail(DDR_ERR_ARG, "period daily: null daily output");
+  if (T < 1) return fail(DDR_ERR_ARG, "period daily: T must be at least 1");
+  if (h0 < 0 || first_hour < 0) return fail(DDR_ERR_ARG, "period daily: h0 and first_hour must not be negative");
+  if (n_days < 1) return fail(DDR_ERR_ARG, "period daily: n_days must be at least 1");
+  const Graph* g = reinterpret_cast<const Graph*>(gh);
+  if (!g->uploaded) return fail(DDR_ERR_ARG, "graph was built host-only: upload it first (ddr_graph_upload)");
+  // a split rank holds the states of its own blocks only: the other rows would be read unwritten
+  if (g->split.nranks > 0) return fail(DDR_ERR_ARG, "split basin: period inference is not supported");
+  PeriodArgs p;
+  p.T = T;
+  p.D = n_days;
+  p.h0 = h0;
+  p.first_hour = first_hour;
+  p.qlb = qlb;
+  period_days(T, n_days, h0, first_hour, &p.d_lo, &p.nd);
+  if (gz && gz->n_gauges > 0 && (!gz->offsets || !gz->index)) return fail(DDR_ERR_ARG, "null gauge arrays");
+  if (p.nd == 0) return DDR_OK;  // no day's window meets this launch
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  if (gz) {
+    GaugeArgs a;
+    ddr_status st = gauge_args<R>(gh, x_save, T, gz, qlb, flags, a);
+    if (st) return st;
+    DDR_TRY(ready_for(g, s));
+    DDR_HIP(launch_period_gauge<R>(a, p, x_save, out, s));
+  } else {
+    DDR_TRY(ready_for(g, s));
+    DDR_HIP(launch_period_all<R>(g, p, (flags & DDR_PERIOD_DIRECT_STORE) != 0, x_save, out, s));
+  }
   return DDR_OK;
 }
 
@@ -1471,6 +1509,17 @@ ddr_status ddr_gauge_daily_seed_f32(int64_t G, int64_t T, int64_t t0, int64_t L,
 ddr_status ddr_gauge_daily_seed_f64(int64_t G, int64_t T, int64_t t0, int64_t L, int64_t D, const double* grad_daily,
                                     double* grad_hourly, void* stream) {
   DDR_GUARD({ return gauge_daily_seed_impl<double>(G, T, t0, L, D, grad_daily, grad_hourly, stream); })
+}
+
+ddr_status ddr_period_daily_f32(const ddr_graph* g, const float* x_save, int64_t T, const ddr_gauges* gz, double qlb,
+                                int32_t flags, int64_t h0, int64_t first_hour, int64_t n_days, float* daily,
+                                void* stream) {
+  DDR_GUARD({ return period_daily_impl<float>(g, x_save, T, gz, qlb, flags, h0, first_hour, n_days, daily, stream); })
+}
+ddr_status ddr_period_daily_f64(const ddr_graph* g, const double* x_save, int64_t T, const ddr_gauges* gz, double qlb,
+                                int32_t flags, int64_t h0, int64_t first_hour, int64_t n_days, double* daily,
+                                void* stream) {
+  DDR_GUARD({ return period_daily_impl<double>(g, x_save, T, gz, qlb, flags, h0, first_hour, n_days, daily, stream); })
 }
 
 ddr_status ddr_geometry_stats_f32(const float* q_daily, int64_t reach_stride, int64_t day_stride, int64_t n,

@@ -444,6 +444,26 @@ ddr_status ddr_gauge_daily_seed_f32(int64_t G, int64_t T, int64_t t0, int64_t L,
 ddr_status ddr_gauge_daily_seed_f64(int64_t G, int64_t T, int64_t t0, int64_t L, int64_t D,
                                     const double* grad_daily, double* grad_hourly, void* stream);
 
+/* Whole-period inference (scripts/router.py:88-201, scripts/test.py:57-112): the daily means of a period
+ * routed in several launches.  Day d of row r is the mean of period hours [first_hour + 24 d,
+ * first_hour + 24 d + 24) (first_hour = 13 + tau, scripts_utils.compute_daily_runoff); one call adds the
+ * hours of one routing launch, period hours [h0, h0 + T), read from that launch's x_save: for every (row,
+ * day) whose window meets the range it sums the shared hours in ascending order -- from 0 if they hold
+ * the window's first hour, else from the partial sum already in daily[r, d] -- and divides by 24 if they
+ * hold the window's last hour.  Calls are stream-ordered, one per launch in period order, so a finished
+ * day is bit-identical to one sequential pass over its 24 hours whatever the chunking; days no call
+ * touches are left alone (the buffer needs no clearing).  gauges == NULL: every reach, reference order,
+ * the value ddr_mc_forward's (N, T) runoff holds; else the gauge sums of ddr_gauge_reduce.  daily is
+ * (R, n_days) row-major; flags: DDR_FWD_CARRY as the forward was run
+ * (DDR_PERIOD_DIRECT_STORE: the all-reach variant that stores per thread, for A/B timing). */
+enum { DDR_PERIOD_DIRECT_STORE = 1 << 24 };
+ddr_status ddr_period_daily_f32(const ddr_graph* g, const float* x_save, int64_t T, const ddr_gauges* gauges,
+                                double discharge_lb, int32_t flags, int64_t h0, int64_t first_hour,
+                                int64_t n_days, float* daily, void* stream);
+ddr_status ddr_period_daily_f64(const ddr_graph* g, const double* x_save, int64_t T, const ddr_gauges* gauges,
+                                double discharge_lb, int32_t flags, int64_t h0, int64_t first_hour,
+                                int64_t n_days, double* daily, void* stream);
+
 /* Per-reach temporal statistics of the trapezoid geometry (src/ddr/geometry/statistics.py:20-83):
  * q_daily holds the daily accumulated discharge, element (reach, day) at
  * reach * reach_stride + day * day_stride (1 <= days <= 32768); out is (24, n): for the variables
