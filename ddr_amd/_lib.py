@@ -96,6 +96,15 @@ class GeomSlot(C.Structure):
 _P = C.c_void_p
 _I64 = C.c_int64
 _I32 = C.c_int32
+
+ATTR_MAX_FEATURES = 64  # DDR_ATTR_MAX_FEATURES
+FLOWPATH_ARRAYS = 5     # DDR_FLOWPATH_ARRAYS: length, slope, x, top_width, side_slope
+
+
+class Flowpath(C.Structure):
+    _fields_ = [("src", _P * FLOWPATH_ARRAYS), ("out", _P * FLOWPATH_ARRAYS), ("fill", C.c_float * FLOWPATH_ARRAYS)]
+
+
 _SIGS = {
     "ddr_graph_build": (C.c_int, [_I64, _I64, _P, _P, C.POINTER(BuildOpts), C.POINTER(C.c_void_p)]),
     "ddr_graph_build_device": (C.c_int, [_I64, _I64, _P, _P, C.POINTER(BuildOpts), _P, C.POINTER(C.c_void_p)]),
@@ -152,6 +161,11 @@ _SIGS = {
     "ddr_summedq_f32": (C.c_int, [_P, _P, _I64, _I64, _I64, _I32, _P, _I64, _P, _I64, _P]),
     "ddr_feed_qprime_f32": (C.c_int, [_P, _I64, _I64, _I64, _P, _I64, _I64, _I64, _I32, _I64, C.c_float, _P, _P, _P]),
     "ddr_feed_rows_f32": (C.c_int, [_P, _I64, _I64, _I64, _P, _I64, _I64, _I64, _I32, _P, _I64, _P, _P]),
+    "ddr_feed_attributes_f32": (C.c_int, [_P, _I64, _I64, _I32, _P, _I64, _P, _P, _P, _P, _P, C.POINTER(Flowpath), _P,
+                                          _P]),
+    "ddr_feed_attr_mean_work_bytes": (_I64, [_I32]),
+    "ddr_feed_attr_mean_f32": (C.c_int, [_P, _I64, _I64, _I32, _P, _I64, _P, _I32, _P, _P, _I64, _P]),
+    "ddr_feed_flow_scale_f32": (C.c_int, [_P, _P, _I64, _P, _P, _I64, _I64, _P, _P, _P]),
     "ddr_upstream_index_create": (C.c_int, [_I64, _I64, _P, _P, _I32, _P, C.POINTER(C.c_void_p)]),
     "ddr_upstream_index_destroy": (C.c_int, [_P]),
     "ddr_upstream_index_info": (C.c_int, [_P, C.POINTER(UpstreamInfo)]),

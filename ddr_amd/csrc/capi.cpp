@@ -19,6 +19,7 @@
 #include "bmi.h"
 #include "upstream.h"
 #include "feed.h"
+#include "attrs.h"
 #include "period.h"
 
 namespace ddr {
@@ -1294,6 +1295,32 @@ ddr_status ddr_feed_rows_f32(const float* store, int64_t row_stride, int64_t n_r
   DDR_GUARD({
     return feed_rows(store, row_stride, n_rows, n_store_cols, rows, n_out_rows, t0, n_cols, trim, out, out_stride,
                      has_nan, static_cast<hipStream_t>(stream));
+  })
+}
+ddr_status ddr_feed_attributes_f32(const float* table, int64_t row_stride, int64_t n_conus, int32_t n_attrs,
+                                   const int32_t* active, int64_t n_reaches, const float* fill, const float* means,
+                                   const float* stds, float* spatial, float* normalized, const ddr_flowpath* path,
+                                   float* flow_scale, void* stream) {
+  DDR_GUARD({
+    return feed_attributes(table, row_stride, n_conus, n_attrs, active, n_reaches, fill, means, stds, spatial,
+                           normalized, path, flow_scale, static_cast<hipStream_t>(stream));
+  })
+}
+int64_t ddr_feed_attr_mean_work_bytes(int32_t n_flagged) { return feed_attr_mean_work_bytes(n_flagged); }
+ddr_status ddr_feed_attr_mean_f32(const float* table, int64_t row_stride, int64_t n_conus, int32_t n_attrs,
+                                  const int32_t* active, int64_t n_reaches, const int32_t* flagged, int32_t n_flagged,
+                                  float* fill, void* work, int64_t work_bytes, void* stream) {
+  DDR_GUARD({
+    return feed_attr_mean(table, row_stride, n_conus, n_attrs, active, n_reaches, flagged, n_flagged, fill, work,
+                          work_bytes, static_cast<hipStream_t>(stream));
+  })
+}
+ddr_status ddr_feed_flow_scale_f32(const int32_t* gage_c, const int32_t* scale_rows, int64_t n_gauges,
+                                   const float* factors, const uint8_t* skip, int64_t n_factors, int64_t n_reaches,
+                                   int32_t* winner, float* flow_scale, void* stream) {
+  DDR_GUARD({
+    return feed_flow_scale(gage_c, scale_rows, n_gauges, factors, skip, n_factors, n_reaches, winner, flow_scale,
+                           static_cast<hipStream_t>(stream));
   })
 }
 ddr_status ddr_upstream_index_create(int64_t n, int64_t e, const int32_t* rows, const int32_t* cols, int32_t flags,

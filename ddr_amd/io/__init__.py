@@ -1,8 +1,12 @@
-"""The per-batch forcing feed on the device (mirrors ``ddr.io.readers``; reading the zarr / icechunk stores stays
-host code): the lateral-inflow store and the gauge observations, uploaded once and gathered per batch."""
+"""The per-batch feed on the device (mirrors ``ddr.io.readers`` and the tensor half of ``ddr.geodatazoo``'s
+``collate_fn``; reading the zarr / icechunk stores stays host code): the lateral-inflow store, the gauge observations
+and the catchment attributes with the flowpath arrays, uploaded once and gathered per batch."""
 
+from .attributes import (AttributeBatch, AttributeStore, FlowScaleTable, align_attributes, flow_scale_factors,
+                         flowpath_fill)
 from .stores import (FILL, ObservationStore, RowIndex, StreamflowStore, daily_window, feed_plan, hourly_window,
                      pad_gage_ids)
 
-__all__ = ["FILL", "ObservationStore", "RowIndex", "StreamflowStore", "daily_window", "feed_plan", "hourly_window",
-           "pad_gage_ids"]
+__all__ = ["FILL", "AttributeBatch", "AttributeStore", "FlowScaleTable", "ObservationStore", "RowIndex",
+           "StreamflowStore", "align_attributes", "daily_window", "feed_plan", "flow_scale_factors", "flowpath_fill",
+           "hourly_window", "pad_gage_ids"]

@@ -580,6 +580,61 @@ ddr_status ddr_feed_rows_f32(const float* store, int64_t row_stride, int64_t n_r
                              const int32_t* rows, int64_t n_out_rows, int64_t t0, int64_t n_cols, int32_t trim,
                              float* out, int64_t out_stride, uint8_t* has_nan, void* stream);
 
+/* The per-batch attribute feed: the catchment attributes, flowpath tensors and flow_scale of a batch, gathered on the
+ * device by the batch's CONUS indices (`active`, device int32, e.g. the active list of ddr_upstream_collate) in place
+ * of the reference's per-batch host code (src/ddr/geodatazoo/merit.py:92-124 _get_attributes, 273-319
+ * _build_common_tensors; lynker_hydrofabric.py:105-135, 302-354; io/readers.py:299-362 build_flow_scale_tensor).
+ * `table` is the attribute store aligned to CONUS order once, device fp32 (n_conus, n_attrs) reach-major, row i at
+ * table + i * row_stride (elements, row_stride >= n_attrs), NaN for a missing value and for every attribute of a reach
+ * the store lacks.  An active[i] outside [0, n_conus) is a missing reach, never an address.  Values are copied as
+ * bits.  Work is queued on `stream`: no allocation, no host sync (capturable).
+ *
+ * ddr_feed_attributes_f32, one launch:
+ *     v              = table[active[i]][a]; a NaN becomes fill[a]
+ *     spatial[a][i]  = v                                     (n_attrs, n_reaches)
+ *     normalized[i][a] = (v - means[a]) / stds[a]            (n_reaches, n_attrs); one fp32 subtraction and one IEEE
+ *                      division; a NaN result carries the bits the reference's host code gives it (the NaN of
+ *                      means[a], else of v, else of stds[a], quieted; 0xffc00000 for inf - inf and 0 / 0)
+ *   fill, means, stds are device fp32 (n_attrs).  fill[a] is means[a] (fill_nans, merit.py:124) except where means[a]
+ *   is NaN: there it is the NaN-mean of the attribute over this batch (merit.py:295-298), which ddr_feed_attr_mean_f32
+ *   writes into it before this call.
+ *   path (host struct, may be null): the flowpath arrays in the order length, slope, x, top_width, side_slope.
+ *     out[k][i] = src[k][active[i]], and fill[k] for a NaN or an out-of-range index (no clamping); src[k] null with
+ *     out[k] set writes the constant fill[k] (MERIT's x = 0.3); out[k] null skips the array.  src / out are device
+ *     fp32 of n_conus / n_reaches elements.
+ *   flow_scale (device fp32 (n_reaches), may be null) is set to 1.0.
+ * ddr_feed_attr_mean_f32: for each of the n_flagged attributes flagged[j] (device int32), fill[flagged[j]] = the mean
+ *   of the batch's non-NaN values of that attribute, accumulated in fp64 in a fixed order (no atomics) and rounded to
+ *   fp32 once; 0xffc00000 when the batch holds none.  `work`: device scratch of ddr_feed_attr_mean_work_bytes(n_flagged)
+ *   bytes, 8-byte aligned.  Two launches; n_flagged = 0 launches nothing.
+ * ddr_feed_flow_scale_f32: the reference's loop over the batch's gauges on a flow_scale that holds ones:
+ *     for g in batch order: flow_scale[gage_c[g]] = factors[scale_rows[g]]
+ *   skipping a gauge whose scale_rows[g] lies outside [0, n_factors) (an unknown gauge), whose skip[scale_rows[g]] is
+ *   set (skip: device uint8 (n_factors), may be null) or whose gage_c[g] lies outside [0, n_reaches).  Of several
+ *   gauges on one segment the last one in batch order that is not skipped wins, whatever the scheduling.  `winner` is
+ *   device int32 scratch (n_reaches), uninitialised.  One launch of one workgroup; n_gauges = 0 launches nothing.
+ * Refused with DDR_ERR_ARG before any launch: negative sizes, n_attrs outside [1, DDR_ATTR_MAX_FEATURES], row_stride <
+ * n_attrs, n_conus or n_gauges beyond int32, n_flagged outside [0, n_attrs], a short or misaligned work buffer, a
+ * flowpath source without an output, null pointers where data is required.  Zero reaches is a no-op. */
+#define DDR_ATTR_MAX_FEATURES 64
+#define DDR_FLOWPATH_ARRAYS 5
+typedef struct ddr_flowpath {
+  const float* src[DDR_FLOWPATH_ARRAYS];
+  float* out[DDR_FLOWPATH_ARRAYS];
+  float fill[DDR_FLOWPATH_ARRAYS];
+} ddr_flowpath;
+ddr_status ddr_feed_attributes_f32(const float* table, int64_t row_stride, int64_t n_conus, int32_t n_attrs,
+                                   const int32_t* active, int64_t n_reaches, const float* fill, const float* means,
+                                   const float* stds, float* spatial, float* normalized, const ddr_flowpath* path,
+                                   float* flow_scale, void* stream);
+int64_t ddr_feed_attr_mean_work_bytes(int32_t n_flagged);
+ddr_status ddr_feed_attr_mean_f32(const float* table, int64_t row_stride, int64_t n_conus, int32_t n_attrs,
+                                  const int32_t* active, int64_t n_reaches, const int32_t* flagged, int32_t n_flagged,
+                                  float* fill, void* work, int64_t work_bytes, void* stream);
+ddr_status ddr_feed_flow_scale_f32(const int32_t* gage_c, const int32_t* scale_rows, int64_t n_gauges,
+                                   const float* factors, const uint8_t* skip, int64_t n_factors, int64_t n_reaches,
+                                   int32_t* winner, float* flow_scale, void* stream);
+
 /* The upstream index: everything upstream of a set of reaches, from the network's COO alone.  It replaces the
  * per-gauge rx.ancestors of the reference (engine/src/ddr_engine/merit/build.py:206-290 build_gauge_adjacencies,
  * graph.py:89-115 subset_upstream; src/ddr/geodatazoo/merit.py:321-396 _build_routing_data_target_catchments; the
