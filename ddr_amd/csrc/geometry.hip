@@ -202,8 +202,24 @@ __device__ __forceinline__ float wave_elem(const float (&v)[KD], int idx) {
 struct DayGeom {
   float depth, tw, bw, ss, Rh;
 };
-__device__ __forceinline__ DayGeom day_geometry(const ReachStatic<float>& s, float Q, const Consts<float>& c) {
+
+// pow_pos and the med3 clamps take a positive finite argument; outside 0 <= Q < inf torch.pow and torch.clamp's
+// NaN propagation define the day: a negative discharge has NaN depth (a negative base under a fractional
+// exponent) and with it NaN geometry, while the discharge itself stays a valid value; +inf has infinite depth
+// and top width and NaN (inf / inf) side slope, bottom width and hydraulic radius; a NaN discharge is NaN
+// everywhere.  geom_domain_q is the discharge to evaluate: Q itself inside the domain (-0 as +0; the pow of a
+// zero lies below any depth bound, where torch's 0 lands too), 1 outside it, where geom_outside then gives
+// the value of geometry variable `var` (0 .. 4).
+__device__ __forceinline__ bool geom_in_domain(float Q) { return Q >= 0.0f && Q < __builtin_inff(); }
+__device__ __forceinline__ float geom_domain_q(float Q) { return geom_in_domain(Q) ? __builtin_fabsf(Q) : 1.0f; }
+__device__ __forceinline__ float geom_outside(float Q, int var) {
+  return (Q == __builtin_inff() && var <= 1) ? __builtin_inff() : __builtin_nanf("");
+}
+
+__device__ __forceinline__ DayGeom day_geometry(const ReachStatic<float>& s, float Qin, const Consts<float>& c) {
   DayGeom g;
+  const bool inside = geom_in_domain(Qin);
+  const float Q = geom_domain_q(Qin);
   const float num = (Q * s.n) * s.qe1();
   const float ratio = dvf<false>(num, s.dd);
   const float pwv = pwf<false>(ratio, s.expo, nullptr, c.pk);
@@ -218,6 +234,11 @@ __device__ __forceinline__ DayGeom day_geometry(const ReachStatic<float>& s, flo
   const float sq = sqrt_rn_normal(1.0f + g.ss * g.ss);
   const float wp = g.bw + (2.0f * g.depth) * sq;
   g.Rh = dvf<false>(area, wp);
+  if (!inside) {
+    g.depth = geom_outside(Qin, 0);
+    g.tw = geom_outside(Qin, 1);
+    g.bw = g.ss = g.Rh = geom_outside(Qin, 2);
+  }
   return g;
 }
 
@@ -386,8 +407,8 @@ __device__ __forceinline__ float geo_var(const GeoArgs& a, const ReachStatic<flo
   if (var == 5) return Q;
   float c1, c2, c3, c4, tw, ss;
   Geom<float> g;
-  coefficients<float, false>(st, Q, cs, c1, c2, c3, c4, tw, ss, &g);
-  if (Q != Q) return __builtin_nanf("");
+  coefficients<float, false>(st, geom_domain_q(Q), cs, c1, c2, c3, c4, tw, ss, &g);
+  if (!geom_in_domain(Q)) return geom_outside(Q, var);  // (a NaN discharge included)
   return var == 0 ? g.depth : (var == 1 ? g.tw : (var == 2 ? g.bw : (var == 3 ? g.ss : g.Rh)));
 }
 

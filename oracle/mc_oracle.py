@@ -431,17 +431,21 @@ def accumulate_daily(net: Network, q_daily: np.ndarray, bd: Bounds = Bounds()) -
     return out
 
 
-def geometry_statistics(n, p, q, slope, daily_q: np.ndarray, bd: Bounds = Bounds()) -> dict:
+def geometry_statistics(n, p, q, slope, daily_q: np.ndarray, bd: Bounds = Bounds(), return_days: bool = False):
     """``src/ddr/geometry/statistics.py:20-83``: per-day trapezoid geometry (trapezoidal.py:62-97, fp32
     reference order, correctly rounded pow) and per-reach nanmin / nanmax / nanmedian / nanmean over
-    the days, for depth, top_width, bottom_width, side_slope, hydraulic_radius and discharge."""
+    the days, for depth, top_width, bottom_width, side_slope, hydraulic_radius and discharge.
+
+    With ``return_days`` the result is ``(statistics, days)``: ``days`` maps each of the six variables to
+    the (D, N) fp32 per-day values the statistics were taken over."""
     f = np.float32
     D, N = daily_q.shape
     geo = {k: np.empty((D, N), dtype=f) for k in ("depth", "top_width", "bottom_width", "side_slope",
                                                     "hydraulic_radius")}
     for d in range(D):
-        g = trapezoid_celerity(np.asarray(daily_q[d], f), np.asarray(n, f), np.asarray(q, f), np.asarray(p, f),
-                               np.asarray(slope, f), bd, f, full=True)
+        with np.errstate(all="ignore"):  # negative or infinite discharge: NaN geometry, as torch gives
+            g = trapezoid_celerity(np.asarray(daily_q[d], f), np.asarray(n, f), np.asarray(q, f), np.asarray(p, f),
+                                   np.asarray(slope, f), bd, f, full=True)
         geo["depth"][d], geo["top_width"][d], geo["bottom_width"][d] = g["depth"], g["tw"], g["bw"]
         geo["side_slope"][d], geo["hydraulic_radius"][d] = g["ss"], g["R"]
     out = {}
@@ -455,6 +459,8 @@ def geometry_statistics(n, p, q, slope, daily_q: np.ndarray, bd: Bounds = Bounds
                 out[f"{name}_max"] = np.nanmax(arr, axis=0).astype(f)
                 out[f"{name}_median"] = np.nanmedian(arr, axis=0).astype(f)
                 out[f"{name}_mean"] = np.nanmean(arr, axis=0).astype(f)
+    if return_days:
+        return out, {**geo, "discharge": np.asarray(daily_q, f)}
     return out
 
 

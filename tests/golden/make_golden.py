@@ -16,6 +16,8 @@ Fixtures:
   csr.npz       F6  canonical CSR + PatternMapper (crow, col) for the F3 and F5 graphs
   geostats.npz  F7  reference compute_geometry_statistics (statistics.py:20-83): 150 reaches x 31 and
                     x 30 days (odd / even median), NaN discharge entries, default and mock bounds
+  geostats_edges.npz  the same on 40 reaches x 70 days with negative, zero, +inf and NaN days, an all-NaN
+                    reach, default and (depth 0.5, bottom_width 0.1) bounds
   collate.npz   F9  per-batch gauge union: reference builders.construct_network_matrix + the network
                     half of Merit._collate_gages (merit.py:197-238) on a synthetic 3k-reach CONUS with
                     12 gauge subsets (nested gauges, a headwater gauge, a gauge missing from the store)
@@ -222,6 +224,41 @@ def make_geostats():
                 out[f"d{D}_{tag}_{k}"] = v
         out[f"d{D}_q"] = dq
     np.savez_compressed(HERE / "geostats.npz", **out)
+
+
+def make_geostats_edges():
+    """The reference's compute_geometry_statistics on the value classes geostats.npz lacks: negative
+    discharge (pow gives NaN geometry while the discharge itself stays valid), exact zeros, one +inf day,
+    NaN days and an all-NaN reach; 40 reaches x 70 days, both minimum sets."""
+    stats, _ = load_objective_modules()
+    rng = np.random.default_rng(78)
+    N, D = 40, 70
+    n = rng.uniform(0.015, 0.25, N).astype(np.float32)
+    p = rng.uniform(1.0, 200.0, N).astype(np.float32)
+    q = rng.uniform(0.0, 1.0, N).astype(np.float32)
+    slope = rng.uniform(1e-3, 0.05, N).astype(np.float32)
+    dq = rng.lognormal(0.0, 3.0, (D, N)).astype(np.float32)
+    dq[rng.random((D, N)) < 0.03] = np.nan
+    for r in range(0, N, 3):  # negative days, 1 to D / 2 of them
+        days = rng.choice(D, int(rng.integers(1, D // 2 + 1)), replace=False)
+        dq[days, r] = -np.abs(dq[days, r])
+    dq[rng.random((D, N)) < 0.02] = 0.0
+    dq[:, 9] = -rng.lognormal(0.0, 1.0, D).astype(np.float32)  # no valid geometry, valid discharge
+    dq[:, 11] = 0.0
+    for r in (4, 12, 21):
+        dq[int(rng.integers(D)), r] = np.inf
+    dq[:, 7] = np.nan  # a reach with no valid day
+    out = dict(n=n, p=p, q=q, slope=slope, daily_q=dq)
+    for tag, mins in (("default", {"depth": 0.01, "bottom_width": 0.01}), ("mock", {"depth": 0.5, "bottom_width": 0.1})):
+        import warnings
+
+        with np.errstate(all="ignore"), warnings.catch_warnings():
+            warnings.simplefilter("ignore", RuntimeWarning)
+            res = stats.compute_geometry_statistics(torch.from_numpy(n), torch.from_numpy(p), torch.from_numpy(q),
+                                                    torch.from_numpy(slope), dq, mins)
+        for k, v in res.items():
+            out[f"{tag}_{k}"] = v
+    np.savez_compressed(HERE / "geostats_edges.npz", **out)
 
 
 def make_daily():
@@ -562,7 +599,7 @@ def make_timestep_geo():
 def main():
     if len(sys.argv) > 1:
         for name in sys.argv[1:]:
-            {"geostats": make_geostats, "daily": make_daily, "collate": make_collate, "deep": make_deep,
+            {"geostats": make_geostats, "geostats_edges": make_geostats_edges, "daily": make_daily, "collate": make_collate, "deep": make_deep,
              "state": make_state, "chain": make_chain, "timestep_geo": make_timestep_geo}[name]()
         return
     torch.manual_seed(0)
@@ -614,6 +651,7 @@ def main():
                         t300_mapidx=c3[4], c1_crow=c5[0], c1_col=c5[1], c1_mcrow=c5[2], c1_mcol=c5[3],
                         c1_mapidx=c5[4])
     make_geostats()
+    make_geostats_edges()
     make_daily()
     make_state()
     make_chain()

@@ -126,6 +126,29 @@ def test_geometry_statistics_oracle_matches_reference_golden():
                 assert maxrel(v[ok], ref[ok]) <= 2e-6, (D, tag, k)
 
 
+def test_geometry_statistics_oracle_matches_reference_on_special_values():
+    """geostats_edges.npz (the reference itself on negative, zero, +inf and NaN days and an all-NaN reach):
+    the oracle has the reference's NaN and inf pattern and its values elsewhere."""
+    d = load_golden("geostats_edges")
+    dq = d["daily_q"]
+    assert (dq < 0).any() and (dq == 0).any() and np.isposinf(dq).sum() == 3 and np.isnan(dq).all(axis=0).any()
+    for tag, bd in (("default", O.Bounds()), ("mock", O.Bounds(depth=0.5, bottom_width=0.1))):
+        got, days = O.geometry_statistics(d["n"], d["p"], d["q"], d["slope"], dq, bd, return_days=True)
+        np.testing.assert_array_equal(days["discharge"], dq)
+        # negative discharge: NaN geometry on a valid discharge day (what the statistics then skip)
+        assert np.isnan(days["depth"][dq < 0]).all() and not np.isnan(days["depth"][dq >= 0]).any()
+        for k, v in got.items():
+            ref = d[f"{tag}_{k}"]
+            assert np.array_equal(np.isnan(v), np.isnan(ref)), (tag, k)
+            assert np.array_equal(np.isinf(v), np.isinf(ref)), (tag, k)
+            np.testing.assert_array_equal(v[np.isinf(ref)], ref[np.isinf(ref)])
+            np.testing.assert_array_equal(v[ref == 0], ref[ref == 0])  # (zero discharge statistics)
+            ok = np.isfinite(ref) & (ref != 0)
+            # correctly rounded pow vs the reference's 1-ulp Sleef powf
+            assert maxrel(v[ok], ref[ok]) <= 2e-6, (tag, k)
+        assert np.isinf(got["depth_max"]).sum() == 3 and np.isnan(got["side_slope_min"][9])
+
+
 def test_daily_objective_oracle_matches_reference_golden():
     """oracle.daily_l1_objective restates train.py:78-97 (downsample + NaN-gauge mask + L1 + warmup)."""
     d = load_golden("daily")
