@@ -191,7 +191,7 @@ _SIGS = {
     "ddr_bmi_window_f32": (C.c_int, [_I64, _I32, _I32, _I32, _P, _P, _P, _I64, _P]),
     "ddr_bmi_outputs_f32": (C.c_int, [_I64, _P, _P, _P, _P, _I64, _P, _P, _P, C.c_double, C.c_double, _P, _I64, _P]),
     "ddr_clip_adam_work_bytes": (_I64, []),
-    "ddr_clip_adam_f32": (C.c_int, [_I64, _P, _P, _P, _P, C.c_float, C.c_float, C.c_float, C.c_float, _P,
+    "ddr_clip_adam_f32": (C.c_int, [_I64, _P, _P, _P, _P, C.c_float, C.c_double, C.c_double, C.c_float, _P,
                                     C.c_float, _P, _P, _P]),
     "ddr_state_f32": (C.c_int, [_P, _P, _I64, _I64, C.c_double, _I32, _P, _P]),
     "ddr_state_f64": (C.c_int, [_P, _P, _I64, _I64, C.c_double, _I32, _P, _P]),

@@ -710,12 +710,12 @@ ddr_status metrics_impl(int64_t n_gauges, int64_t n_days, const float* pred, int
                          static_cast<hipStream_t>(stream)));
   return DDR_OK;
 }
-ddr_status clip_adam_impl(int64_t n, float* params, const float* grad, float* m, float* v, float lr, float beta1,
-                          float beta2, float eps, float* step, float max_norm, float* norm_out, void* work,
+ddr_status clip_adam_impl(int64_t n, float* params, const float* grad, float* m, float* v, float lr, double beta1,
+                          double beta2, float eps, float* step, float max_norm, float* norm_out, void* work,
                           void* stream) {
   if (n < 0) return fail(DDR_ERR_ARG, "clip_adam: negative size");
   if (n > 0 && (!params || !grad || !m || !v)) return fail(DDR_ERR_ARG, "clip_adam: null argument");
-  if (!(beta1 >= 0.0f && beta1 < 1.0f) || !(beta2 >= 0.0f && beta2 < 1.0f)) return fail(DDR_ERR_ARG, "clip_adam: betas in [0, 1)");
+  if (!(beta1 >= 0.0 && beta1 < 1.0) || !(beta2 >= 0.0 && beta2 < 1.0)) return fail(DDR_ERR_ARG, "clip_adam: betas in [0, 1)");
   if (!step || !work) return fail(DDR_ERR_ARG, "clip_adam: null step counter or workspace (ddr_clip_adam_work_bytes)");
   DDR_HIP(launch_clip_adam(n, params, grad, m, v, lr, beta1, beta2, eps, step, max_norm, norm_out, work,
                            static_cast<hipStream_t>(stream)));
@@ -1497,8 +1497,8 @@ ddr_status ddr_bmi_outputs_f32(int64_t n_segments, const float* discharge, const
   })
 }
 int64_t ddr_clip_adam_work_bytes(void) { return (int64_t)clip_adam_work_bytes(); }
-ddr_status ddr_clip_adam_f32(int64_t n, float* params, const float* grad, float* m, float* v, float lr, float beta1,
-                             float beta2, float eps, float* step, float max_norm, float* norm_out, void* work,
+ddr_status ddr_clip_adam_f32(int64_t n, float* params, const float* grad, float* m, float* v, float lr, double beta1,
+                             double beta2, float eps, float* step, float max_norm, float* norm_out, void* work,
                              void* stream) {
   DDR_GUARD({ return clip_adam_impl(n, params, grad, m, v, lr, beta1, beta2, eps, step, max_norm, norm_out, work, stream); })
 }

@@ -9,9 +9,9 @@
 namespace ddr {
 hipError_t launch_daily_l1(int64_t G, int64_t D, int64_t wd, const float* daily, const float* obs, float inv_count,
                            float* loss, float* grad, hipStream_t stream);
-// device scratch of launch_clip_adam (per-workgroup partial sums of squares)
+// device scratch of launch_clip_adam (per-workgroup partial sums of squares, the step's two bias corrections)
 size_t clip_adam_work_bytes();
-hipError_t launch_clip_adam(int64_t n, float* param, const float* grad, float* m, float* v, float lr, float beta1,
-                            float beta2, float eps, float* step, float max_norm, float* norm_out, void* work,
+hipError_t launch_clip_adam(int64_t n, float* param, const float* grad, float* m, float* v, float lr, double beta1,
+                            double beta2, float eps, float* step, float max_norm, float* norm_out, void* work,
                             hipStream_t stream);
 }  // namespace ddr

@@ -58,11 +58,13 @@ struct AdamArgs {
   const float* grad;
   float* m;
   float* v;
-  float lr, beta1, beta2, eps;
+  float lr, eps;
+  double beta1, beta2;  // as given (torch keeps them in double): 1 - beta is formed before the rounding to fp32
   float* step;      // device step counter (fp32, like torch's capturable Adam): incremented by this update
   float max_norm;   // <= 0: no clipping
   float* norm_out;  // the gradient's total norm before clipping (clip_grad_norm_'s return value), or null
-  double* partial;  // [kAdamWgs] per-workgroup sums of squares
+  // [kAdamWgs] per-workgroup sums of squares, then this step's lr / (1 - beta1^t) and sqrt(1 - beta2^t)
+  double* partial;
 };
 
 // Two launches over kAdamWgs workgroups (a single workgroup spent ~40 us on a 34k-parameter vector in
@@ -91,16 +93,24 @@ __global__ void __launch_bounds__(kAdamThreads) adam_norm_kernel(AdamArgs a) {
   }
   const double s = block_sum256(ss, red);
   if (threadIdx.x == 0) a.partial[blockIdx.x] = s;
-  if (blockIdx.x == 0 && threadIdx.x == 0) a.step[0] = a.step[0] + 1.0f;  // read by adam_step_kernel, next launch
+  if (blockIdx.x == 0 && threadIdx.x == 0) {
+    // the step counter and the bias corrections of this step, once (read by adam_step_kernel, next launch), from
+    // the double betas as torch.optim.Adam forms them: the moments' weights are fp32(1 - beta), so 1 - beta^t has
+    // to be of the same beta (1 - fp32(0.999) is 1.3e-5 off 1e-3)
+    const float t = a.step[0] + 1.0f;
+    a.step[0] = t;
+    a.partial[kAdamWgs] = (double)a.lr / (1.0 - pow(a.beta1, (double)t));
+    a.partial[kAdamWgs + 1] = sqrt(1.0 - pow(a.beta2, (double)t));
+  }
 }
 
 __global__ void __launch_bounds__(kAdamThreads) adam_step_kernel(AdamArgs a) {
   __shared__ float coef_s, step_s, bc2s_s;
   if (threadIdx.x == 0) {
-    // bias corrections of this step on the device (torch's capturable Adam: fp32 step tensor)
-    const float t = a.step[0];
-    step_s = a.lr / (1.0f - powf(a.beta1, t));
-    bc2s_s = sqrtf(1.0f - powf(a.beta2, t));
+    // bias corrections of this step, formed on the device by adam_norm_kernel (torch's capturable Adam: fp32 step
+    // tensor)
+    step_s = (float)a.partial[kAdamWgs];
+    bc2s_s = (float)a.partial[kAdamWgs + 1];
     double s = 0.0;
     for (int w = 0; w < kAdamWgs; ++w) s += a.partial[w];
     const float norm = (float)sqrt(s);
@@ -110,11 +120,11 @@ __global__ void __launch_bounds__(kAdamThreads) adam_step_kernel(AdamArgs a) {
   }
   __syncthreads();
   const float coef = coef_s, step = step_s, bc2_sqrt = bc2s_s;
-  const float omb1 = 1.0f - a.beta1, omb2 = 1.0f - a.beta2;
+  const float omb1 = (float)(1.0 - a.beta1), omb2 = (float)(1.0 - a.beta2), beta2 = (float)a.beta2;
   for (int64_t i = (int64_t)blockIdx.x * kAdamThreads + threadIdx.x; i < a.n; i += (int64_t)kAdamWgs * kAdamThreads) {
     const float g = a.grad[i] * coef;
     const float m = fmaf(omb1, g - a.m[i], a.m[i]);           // exp_avg.lerp_(grad, 1 - beta1)
-    const float v = fmaf(a.beta2, a.v[i], omb2 * g * g);      // exp_avg_sq * beta2 + (1 - beta2) g^2
+    const float v = fmaf(beta2, a.v[i], omb2 * g * g);        // exp_avg_sq * beta2 + (1 - beta2) g^2
     a.m[i] = m;
     a.v[i] = v;
     const float den = sqrtf(v) / bc2_sqrt + a.eps;
@@ -130,12 +140,12 @@ hipError_t launch_daily_l1(int64_t G, int64_t D, int64_t wd, const float* daily,
   return hipGetLastError();
 }
 
-size_t clip_adam_work_bytes() { return sizeof(double) * kAdamWgs; }
+size_t clip_adam_work_bytes() { return sizeof(double) * (kAdamWgs + 2); }
 
-hipError_t launch_clip_adam(int64_t n, float* param, const float* grad, float* m, float* v, float lr, float beta1,
-                            float beta2, float eps, float* step, float max_norm, float* norm_out, void* work,
+hipError_t launch_clip_adam(int64_t n, float* param, const float* grad, float* m, float* v, float lr, double beta1,
+                            double beta2, float eps, float* step, float max_norm, float* norm_out, void* work,
                             hipStream_t stream) {
-  AdamArgs a{n, param, grad, m, v, lr, beta1, beta2, eps, step, max_norm, norm_out, static_cast<double*>(work)};
+  AdamArgs a{n, param, grad, m, v, lr, eps, beta1, beta2, step, max_norm, norm_out, static_cast<double*>(work)};
   hipLaunchKernelGGL(adam_norm_kernel, dim3(kAdamWgs), dim3(kAdamThreads), 0, stream, a);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return e;

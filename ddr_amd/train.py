@@ -93,7 +93,7 @@ class ClipAdam:
         g = g.contiguous()
         b1, b2 = self.betas
         _lib.check(_lib.load().ddr_clip_adam_f32(self.param.numel(), self.param.data_ptr(), g.data_ptr(),
-                                                 self.m.data_ptr(), self.v.data_ptr(), C.c_float(self.lr), C.c_float(b1),
-                                                 C.c_float(b2), C.c_float(self.eps), self.step_count.data_ptr(),
+                                                 self.m.data_ptr(), self.v.data_ptr(), C.c_float(self.lr), C.c_double(b1),
+                                                 C.c_double(b2), C.c_float(self.eps), self.step_count.data_ptr(),
                                                  C.c_float(self.max_norm), self.last_norm.data_ptr(),
                                                  self.work.data_ptr(), _lib.stream_ptr(self.param.device)))

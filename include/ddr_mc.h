@@ -407,6 +407,8 @@ ddr_status ddr_kan_backward_f32(const ddr_kan_desc* desc, int64_t n_rows, const 
  *   its moments m, v; step is a device fp32 counter (0 before the first step) that the launch increments and
  *   takes the bias corrections from, as torch's capturable Adam does -- no host value, so the launch can be
  *   captured into a graph and replayed.
+ *   beta1, beta2 are doubles, as torch.optim.Adam holds them: the moments' weights are fp32(1 - beta) (1 - fp32(0.999)
+ *   would be 1.3e-5 off) and the bias corrections 1 - beta^step are formed in double.
  *   norm_out (or NULL) receives the gradient's norm before clipping.  grad is not modified.  work: device
  *   scratch of ddr_clip_adam_work_bytes() bytes.
  * Both deterministic (fixed slices and reduction order).
@@ -414,8 +416,8 @@ ddr_status ddr_kan_backward_f32(const ddr_kan_desc* desc, int64_t n_rows, const 
 ddr_status ddr_daily_l1_f32(int64_t n_gauges, int64_t n_days, int64_t warmup, const float* daily, const float* obs,
                             float inv_count, float* loss, float* grad, void* stream);
 int64_t ddr_clip_adam_work_bytes(void);
-ddr_status ddr_clip_adam_f32(int64_t n, float* params, const float* grad, float* m, float* v, float lr, float beta1,
-                             float beta2, float eps, float* step, float max_norm, float* norm_out, void* work,
+ddr_status ddr_clip_adam_f32(int64_t n, float* params, const float* grad, float* m, float* v, float lr, double beta1,
+                             double beta2, float eps, float* step, float max_norm, float* norm_out, void* work,
                              void* stream);
 
 /* Gauge reduction of a forward's saved states x_save: runoff (G, T). */
