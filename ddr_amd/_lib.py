@@ -93,6 +93,13 @@ class GeomSlot(C.Structure):
                 ("value", C.c_double)]
 
 
+class ObjectiveDesc(C.Structure):
+    _fields_ = [("kind", C.c_int32), ("reserved", C.c_int32), ("n_gauges", C.c_int64), ("n_days", C.c_int64),
+                ("warmup", C.c_int64), ("eps", C.c_double)]
+
+
+OBJECTIVE_KINDS = ("l1", "mse", "nse", "kge")  # DDR_OBJECTIVE_* order
+
 _P = C.c_void_p
 _I64 = C.c_int64
 _I32 = C.c_int32
@@ -154,6 +161,9 @@ _SIGS = {
     "ddr_kan_forward_f32": (C.c_int, [C.POINTER(KanDesc), _I64, _P, _P, _P, _P, _P, _P, _P]),
     "ddr_kan_backward_f32": (C.c_int, [C.POINTER(KanDesc), _I64, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "ddr_daily_l1_f32": (C.c_int, [_I64, _I64, _I64, _P, _P, C.c_float, _P, _P, _P]),
+    "ddr_daily_objective_work_bytes": (_I64, [_I64]),
+    "ddr_daily_objective_f32": (C.c_int, [C.POINTER(ObjectiveDesc), _P, _I64, _P, _I64, _P, _P, C.c_double, _P, _P, _P,
+                                          _P, _P, _P]),
     "ddr_metrics_f32": (C.c_int, [_I64, _I64, _P, _I64, _P, _I64, _P, _P, _P]),
     "ddr_summedq_plan_create": (C.c_int, [_I64, _P, _P, _I64, _P, C.POINTER(C.c_void_p)]),
     "ddr_summedq_plan_destroy": (C.c_int, [_P]),

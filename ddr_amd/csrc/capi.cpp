@@ -12,6 +12,7 @@
 #include "internal.h"
 #include "route_args.h"
 #include "metrics.h"
+#include "objective.h"
 #include "train.h"
 #include "kan.h"
 #include "geopredict.h"
@@ -710,6 +711,34 @@ ddr_status metrics_impl(int64_t n_gauges, int64_t n_days, const float* pred, int
                          static_cast<hipStream_t>(stream)));
   return DDR_OK;
 }
+ddr_status daily_objective_impl(const ddr_objective_desc* desc, const float* daily, int64_t daily_stride,
+                                const float* obs, int64_t obs_stride, const uint8_t* drop, const float* weight,
+                                double count, const float* count_dev, float* loss, float* grad, double* terms,
+                                void* work, void* stream) {
+  if (!desc) return fail(DDR_ERR_ARG, "daily_objective: null descriptor");
+  const int64_t G = desc->n_gauges, D = desc->n_days, wd = desc->warmup;
+  if (G < 0 || D < 0 || wd < 0 || daily_stride < 0 || obs_stride < 0)
+    return fail(DDR_ERR_ARG, "daily_objective: negative size");
+  if (desc->kind < 0 || desc->kind >= DDR_N_OBJECTIVES)
+    return fail(DDR_ERR_ARG, "daily_objective: unknown kind " + std::to_string(desc->kind));
+  if (!(desc->eps >= 0.0)) return fail(DDR_ERR_ARG, "daily_objective: eps must be >= 0");
+  if (!(count >= 0.0)) return fail(DDR_ERR_ARG, "daily_objective: count must be >= 0 (0: not given)");
+  if (G == 0) return DDR_OK;
+  if (D < 1 || D > kObjectiveMaxDays)
+    return fail(DDR_ERR_ARG, "daily_objective: 1 <= n_days <= " + std::to_string(kObjectiveMaxDays) + " (got " +
+                                 std::to_string(D) + ")");
+  if (wd >= D)
+    return fail(DDR_ERR_ARG, "daily_objective: warmup " + std::to_string(wd) + " leaves no day of " + std::to_string(D));
+  if (G > kObjectiveMaxGauges) return fail(DDR_ERR_ARG, "daily_objective: too many gauges");
+  if (!daily) return fail(DDR_ERR_ARG, "daily_objective: null daily");
+  if (!obs) return fail(DDR_ERR_ARG, "daily_objective: null obs");
+  if (!loss) return fail(DDR_ERR_ARG, "daily_objective: null loss");
+  if (!work) return fail(DDR_ERR_ARG, "daily_objective: null work (ddr_daily_objective_work_bytes)");
+  ObjectiveArgs a{daily, obs, daily_stride, obs_stride, drop, weight, count_dev, count, G, (int)D, (int)wd,
+                  desc->kind, desc->eps, loss, grad, terms, static_cast<double*>(work)};
+  DDR_HIP(launch_objective(a, static_cast<hipStream_t>(stream)));
+  return DDR_OK;
+}
 ddr_status clip_adam_impl(int64_t n, float* params, const float* grad, float* m, float* v, float lr, double beta1,
                           double beta2, float eps, float* step, float max_norm, float* norm_out, void* work,
                           void* stream) {
@@ -1254,6 +1283,15 @@ ddr_status ddr_daily_l1_f32(int64_t n_gauges, int64_t n_days, int64_t warmup, co
                             float inv_count, float* loss, float* grad, void* stream) {
   DDR_GUARD({ return daily_l1_impl(n_gauges, n_days, warmup, daily, obs, inv_count, loss, grad, stream); })
 }
+ddr_status ddr_daily_objective_f32(const ddr_objective_desc* desc, const float* daily, int64_t daily_stride,
+                                   const float* obs, int64_t obs_stride, const uint8_t* drop, const float* weight,
+                                   double count, const float* count_dev, float* loss, float* grad, double* terms,
+                                   void* work, void* stream) {
+  DDR_GUARD({
+    return daily_objective_impl(desc, daily, daily_stride, obs, obs_stride, drop, weight, count, count_dev, loss, grad,
+                                terms, work, stream);
+  })
+}
 ddr_status ddr_metrics_f32(int64_t n_gauges, int64_t n_days, const float* pred, int64_t pred_stride,
                            const float* target, int64_t target_stride, double* out, int32_t* pred_nan_count,
                            void* stream) {
@@ -1497,6 +1535,10 @@ ddr_status ddr_bmi_outputs_f32(int64_t n_segments, const float* discharge, const
   })
 }
 int64_t ddr_clip_adam_work_bytes(void) { return (int64_t)clip_adam_work_bytes(); }
+int64_t ddr_daily_objective_work_bytes(int64_t n_gauges) {
+  if (n_gauges < 0 || n_gauges > kObjectiveMaxGauges) return -1;
+  return (int64_t)objective_work_bytes(n_gauges);
+}
 ddr_status ddr_clip_adam_f32(int64_t n, float* params, const float* grad, float* m, float* v, float lr, double beta1,
                              double beta2, float eps, float* step, float max_norm, float* norm_out, void* work,
                              void* stream) {

@@ -420,6 +420,58 @@ ddr_status ddr_clip_adam_f32(int64_t n, float* params, const float* grad, float*
                              double beta2, float eps, float* step, float max_norm, float* norm_out, void* work,
                              void* stream);
 
+/* Masked training objectives over the gauges' daily series: the loss and its gradient w.r.t. the predictions with
+ * a NaN observation as a missing day and a dropped gauge as a mask, without a host sync or a change of shape, so a
+ * step on real (gappy) observations can be captured.  Replaces scripts/train.py:84-97 -- the filter that drops
+ * every gauge whose observation window holds a NaN (boolean indexing: a host wait and a new shape per batch),
+ * l1_loss over the rest after the warm-up, and its backward -- and adds per-gauge normalised objectives.
+ *   desc    kind (DDR_OBJECTIVE_*), n_gauges G, n_days D (1 <= D <= 8192), warmup w (0 <= w < D: days excluded),
+ *           eps >= 0 (NSE only).
+ *   daily, obs  device fp32, row g at daily + g * daily_stride / obs + g * obs_stride (strides in elements), D
+ *           values each.  daily is the only differentiated input.
+ *   drop    device (G,) bytes, non-zero: the gauge contributes nothing (ObservationStore.window's has_nan reproduces
+ *           the reference's filter); NULL: none.    weight  device (G,) fp32, >= 0 and finite; NULL: all 1.
+ *   count, count_dev  the normaliser W when the caller knows better (ranks that all-reduce their counts): count_dev,
+ *           a device fp32 scalar read by the launch (a captured step updates it in place), else count > 0 by value;
+ *           count == 0 and count_dev == NULL: W as defined below.
+ * For gauge g, V_g = {d >= w : obs[g, d] is not NaN}, empty when drop[g]; n_g = |V_g|.  Over V_g, in fp64 of the fp32
+ * inputs: A = sum |p - o|, S = sum (p - o)^2, the means mu_p, mu_o, S_pp = sum (p - mu_p)^2, S_oo = sum (o - mu_o)^2,
+ * S_po = sum (p - mu_p)(o - mu_o), sigma = sqrt(S_.. / n_g).
+ *   L1   term A / n_g;  MSE  term S / n_g:  used when n_g >= 1;  loss = sum_used w_g n_g term_g / W, W = sum_used
+ *        w_g n_g (unit weights: the mean over every counted day; with drop = has_nan, L1 is the reference's
+ *        l1_loss(pred[keep][:, w:], target[keep][:, w:])).
+ *   NSE  term S / (n_g (sigma_o + eps)^2), 1 - NSE at eps = 0: used when n_g >= 2 and (S_oo != 0 or eps > 0);
+ *   KGE  term E = sqrt((r - 1)^2 + (alpha - 1)^2 + (beta - 1)^2), r = S_po / sqrt(S_pp S_oo), alpha = sigma_p /
+ *        sigma_o, beta = mu_p / mu_o, 1 - KGE of validation/metrics.py:216-227: used when n_g >= 2 and none of
+ *        S_oo == 0, mu_o == 0, S_pp == 0 holds (a NaN prediction keeps the gauge counted);
+ *        loss = sum_used w_g term_g / W, W = sum_used w_g.
+ * W == 0 (nothing used): loss 0, gradient 0.  A NaN prediction on a day of V_g makes the loss NaN and the gradient
+ * NaN at that element at least (KGE: possibly that gauge's row); other gauges' rows are unchanged.
+ *   loss    device fp32 scalar.
+ *   grad    device fp32 (G, D) row-major or NULL (no gradient launch): d loss / d daily, each element formed in fp64
+ *           and rounded once; exactly +0.0 outside V_g and for every gauge that is not used.  L1: w_g sign(p - o) / W
+ *           (sign(0) = 0);  MSE: 2 w_g (p - o) / W;  NSE: 2 w_g (p - o) / (W n_g (sigma_o + eps)^2);  KGE: (w_g / W)
+ *           [(r - 1) dr + (alpha - 1) dalpha + (beta - 1) dbeta] / E with dr = [(o - mu_o) - r sqrt(S_oo / S_pp)
+ *           (p - mu_p)] / sqrt(S_pp S_oo), dalpha = (p - mu_p) / (n_g sigma_p sigma_o), dbeta = 1 / (n_g mu_o); 0
+ *           where E == 0.
+ *   terms   device fp64 (3, G) or NULL: row 0 the term (NaN when the gauge is not used), row 1 n_g, row 2 used (0/1).
+ *   work    device scratch of ddr_daily_objective_work_bytes(G) bytes (8-byte aligned).
+ * At most three launches on `stream` (moments per gauge; a fixed-order reduction; the gradient), no atomics, no
+ * allocation: results are bitwise repeatable, and a gauge's term and gradient row do not depend on which other
+ * gauges are in the batch beyond W.  n_gauges == 0 is a no-op. */
+enum { DDR_OBJECTIVE_L1 = 0, DDR_OBJECTIVE_MSE, DDR_OBJECTIVE_NSE, DDR_OBJECTIVE_KGE, DDR_N_OBJECTIVES };
+typedef struct ddr_objective_desc {
+  int32_t kind;
+  int32_t reserved; /* 0 */
+  int64_t n_gauges, n_days, warmup;
+  double eps;
+} ddr_objective_desc;
+int64_t ddr_daily_objective_work_bytes(int64_t n_gauges);
+ddr_status ddr_daily_objective_f32(const ddr_objective_desc* desc, const float* daily, int64_t daily_stride,
+                                   const float* obs, int64_t obs_stride, const uint8_t* drop, const float* weight,
+                                   double count, const float* count_dev, float* loss, float* grad, double* terms,
+                                   void* work, void* stream);
+
 /* Gauge reduction of a forward's saved states x_save: runoff (G, T). */
 ddr_status ddr_gauge_reduce_f32(const ddr_graph* g, const float* x_save, int64_t T,
                                 const ddr_gauges* gauges, double discharge_lb, int32_t flags,
