@@ -326,6 +326,61 @@ __global__ void __launch_bounds__(256) k_sub_ht_lds(const int32_t* roots, const 
   }
 }
 
+// The split's "other children in (residual, column) order" for a reach with many inflows.  The per-step selection
+// scan below is quadratic in the child count (one thread, dependent global loads: a 9000-inflow hub took minutes
+// per pass).  In that order the residuals ascend and the budget only shrinks, so the absorbed children are a
+// prefix of it: every child whose residual is below a threshold v, and the first t (column order) of those equal
+// to v.  v is the smallest residual whose cumulative sum F(v) = sum of residuals <= v exceeds the budget
+// L = min(scap - lseg - trib, scap - base), found by bisection over the residuals' range: O(c log scap), the same
+// decisions as graph.cpp's stable sort.  res(j) is the residual of child j (column order), `skip` the stem child,
+// root(j) marks child j a piece root; returns the absorbed mass.
+constexpr int kSelectScanMax = 8;  // up to this many other children: the selection scan
+template <class Res, class Root>
+__device__ __forceinline__ int64_t absorb_wide(int32_t nc, int32_t skip, int64_t L, Res res, Root root) {
+  int64_t total = 0, rmin = 0x7fffffffffffffffll, rmax = 0;
+  for (int32_t j = 0; j < nc; ++j) {
+    if (j == skip) continue;
+    const int64_t r = res(j);
+    total += r;
+    rmin = r < rmin ? r : rmin;
+    rmax = r > rmax ? r : rmax;
+  }
+  if (total <= L) return total;  // (also: no other child)
+  int64_t lo = rmin, hi = rmax;  // F(rmax) = total > L
+  while (lo < hi) {
+    const int64_t mid = lo + (hi - lo) / 2;
+    int64_t F = 0;
+    for (int32_t j = 0; j < nc; ++j) {
+      if (j == skip) continue;
+      const int64_t r = res(j);
+      F += r <= mid ? r : 0;
+    }
+    if (F > L) hi = mid;
+    else lo = mid + 1;
+  }
+  const int64_t v = lo;
+  int64_t below = 0;
+  if (v > rmin)
+    for (int32_t j = 0; j < nc; ++j) {
+      if (j == skip) continue;
+      const int64_t r = res(j);
+      below += r < v ? r : 0;
+    }
+  const int64_t t = L - below >= v ? (L - below) / v : 0;  // of the children at v, the first t fit (not all)
+  int64_t seen = 0;
+  for (int32_t j = 0; j < nc; ++j) {
+    if (j == skip) continue;
+    const int64_t r = res(j);
+    if (r < v) continue;
+    if (r == v && seen < t) {
+      ++seen;
+      continue;
+    }
+    root(j);
+  }
+  return below + t * v;
+}
+
 // Stem-preserving split of the basins larger than scap (graph.cpp build_graph, same rule and the
 // same tie-breaks: the deepest child by (height, size), first in column order; the others by
 // ascending residual size, ties in column order).  Smaller basins stay one piece.
@@ -351,10 +406,13 @@ __global__ void __launch_bounds__(256) k_split(const int32_t* roots, const int32
         stem[i] = ht[i] + 1;
         continue;
       }
-      int32_t dc = col[k0];
+      int32_t dc = col[k0], dk = k0;
       for (int32_t k = k0 + 1; k < k1; ++k) {
         const int32_t c = col[k];
-        if (ht[c] > ht[dc] || (ht[c] == ht[dc] && sub[c] > sub[dc])) dc = c;
+        if (ht[c] > ht[dc] || (ht[c] == ht[dc] && sub[c] > sub[dc])) {
+          dc = c;
+          dk = k;
+        }
       }
       int64_t base = 1 + (int64_t)resid[dc], trib = (int64_t)resid[dc] - stem[dc];
       const bool keep = base <= scap;
@@ -364,6 +422,14 @@ __global__ void __launch_bounds__(256) k_split(const int32_t* roots, const int32
         trib = 0;
       }
       int64_t acc = 0;
+      if (k1 - k0 - 1 > kSelectScanMax) {
+        const int64_t la = scap - lseg - trib, lb = scap - base, L = la < lb ? la : lb;
+        acc = absorb_wide(k1 - k0, dk - k0, L, [&](int32_t j) { return (int64_t)resid[col[k0 + j]]; },
+                          [&](int32_t j) { is_root[col[k0 + j]] = 1; });
+        resid[i] = (int32_t)(base + acc);
+        stem[i] = keep ? 1 + stem[dc] : 1;
+        continue;
+      }
       // the other children in (resid, column position) order: a selection per step (few children)
       int64_t pr = -1, pk = -1;
       for (int32_t step = 0; step < k1 - k0 - 1; ++step) {
@@ -494,6 +560,23 @@ __global__ void __launch_bounds__(256) k_split_lds(const int32_t* roots, const i
         trib = 0;
       }
       int64_t acc = 0;
+      if (nc - 1 > kSelectScanMax) {
+        const int64_t la = scap - lseg - trib, lb = scap - base, L = la < lb ? la : lb;
+        acc = absorb_wide(
+            nc, dj, L,
+            [&](int32_t j) {
+              int32_t cp, ci, cs, ch;
+              child(j, cp, ci, cs, ch);
+              return (int64_t)get_res(cp, ci);
+            },
+            [&](int32_t j) {
+              int32_t cp, ci, cs, ch;
+              child(j, cp, ci, cs, ch);
+              is_root[ci] = 1;
+            });
+        put(p, i, (int32_t)(base + acc), keep ? 1 + dstem : 1);
+        return;
+      }
       // the other children in (resid, column position) order: a selection per step (few children)
       int64_t pr = -1, pk = -1;
       for (int32_t stp = 0; stp < nc - 1; ++stp) {

@@ -35,6 +35,9 @@ Fixtures:
   daily.npz     F8  the training objective of scripts/train.py:78-97 on a (7, 2136) gauge series:
                     downsample(runoff[:, 13:-8], 88) (io/functions.py:7-23), NaN-gauge mask, L1 with
                     warmup 3, and torch autograd's d loss / d runoff
+  confluence.npz  a 300-reach tree with in-degrees up to 20 (tests/confluence_cases.py bushy) x 48 steps: outputs
+                    and gradients, a carried second leg, a gauge-mode run with gauges on confluences, and
+                    the CSR + PatternMapper layout
 
 Run:  python tests/golden/make_golden.py [geostats daily]   (no argument: all fixtures)
 """
@@ -596,11 +599,47 @@ def make_timestep_geo():
                         **{f"ref_grad_{k}": v.grad.numpy().copy() for k, v in sp.items()})
 
 
+def make_confluence():
+    """The reference on a network whose reaches take up to 20 inflows (tests/confluence_cases.py ``bushy``; the
+    other routing fixtures stop at two): 300 reaches x 48 steps, learned n / q / p, per-reach outputs; a second
+    leg carried from the first one's final state; a hot-started gauge-mode run with gauges on confluences; and
+    the canonical CSR + PatternMapper layout.  q' and W are regenerated from their seeds by the tests
+    (``confluence_cases.golden_confluence``), which check the stored sums."""
+    sys.path.insert(0, str(HERE.parent))
+    import confluence_cases as cc
+
+    torch.manual_seed(0)
+    _, mmc = load_reference()
+    seed, T = cc.GOLDEN_SEED, cc.T
+    net = cc.bushy(cc.GOLDEN_N, seed)
+    inputs, res, mc, dc = case(mmc, PARAMS_DEFAULT, net, T, seed)
+    u = {k: inputs[f"u_{k}"] for k in ("n", "q_spatial", "p_spatial")}
+    q2 = synthetic.lateral_inflow(net.n, T, seed, t0=T)
+    W2 = np.random.default_rng(cc.GOLDEN_W2_SEED).uniform(0, 1, (net.n, T)).astype(np.float32)
+    res2, _ = run_ref(mmc, PARAMS_DEFAULT, dc, q2, u, W2, carry_from=mc._discharge_t.detach().clone())
+    outflow = cc.golden_gauges(net)
+    inputs_g, res_g, _, _ = case(mmc, PARAMS_DEFAULT, net, T, seed, outflow_idx=outflow)
+    for k in ("length", "slope", "x", "qprime", "u_n", "u_q_spatial", "u_p_spatial"):
+        np.testing.assert_array_equal(inputs[k], inputs_g[k])
+    c = mapper_csr(mmc, net.n, net.rows, net.cols)
+    small = {k: v for k, v in inputs.items() if k not in ("qprime", "W")}
+    f8 = lambda a: np.float64(a.astype(np.float64).sum())  # noqa: E731
+    np.savez_compressed(HERE / "confluence.npz", **small, T=np.int64(T), qprime_sum=f8(inputs["qprime"]),
+                        W_sum=f8(inputs["W"]), qprime2_sum=f8(q2), W2_sum=f8(W2), Wg_sum=f8(inputs_g["W"]),
+                        outflow_flat=np.concatenate(outflow).astype(np.int64),
+                        outflow_offsets=np.cumsum([0] + [len(o) for o in outflow]).astype(np.int64),
+                        **{f"ref_{k}": v for k, v in res.items()}, **{f"ref2_{k}": v for k, v in res2.items()},
+                        **{f"refg_{k}": v for k, v in res_g.items()},
+                        crow=c[0], col=c[1], mcrow=c[2], mcol=c[3], mapidx=c[4])
+    print("confluence.npz", (HERE / "confluence.npz").stat().st_size)
+
+
 def main():
     if len(sys.argv) > 1:
         for name in sys.argv[1:]:
             {"geostats": make_geostats, "geostats_edges": make_geostats_edges, "daily": make_daily, "collate": make_collate, "deep": make_deep,
-             "state": make_state, "chain": make_chain, "timestep_geo": make_timestep_geo}[name]()
+             "state": make_state, "chain": make_chain, "timestep_geo": make_timestep_geo,
+             "confluence": make_confluence}[name]()
         return
     torch.manual_seed(0)
     utils, mmc = load_reference()
