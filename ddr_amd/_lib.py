@@ -100,6 +100,13 @@ class ObjectiveDesc(C.Structure):
 
 OBJECTIVE_KINDS = ("l1", "mse", "nse", "kge")  # DDR_OBJECTIVE_* order
 
+# ddr_summary_*: the columns before the quantiles (DDR_SUMMARY_*), the methods (DDR_SUMMARY_LINEAR, _LOWER), the flag
+SUMMARY_COLUMNS = ("count", "min", "max", "mean", "std")
+SUMMARY_METHODS = ("linear", "lower")
+SUMMARY_SKIP_INF = 1
+SUMMARY_MAX_Q = 8
+SUMMARY_TILE = 4096
+
 _P = C.c_void_p
 _I64 = C.c_int64
 _I32 = C.c_int32
@@ -165,6 +172,9 @@ _SIGS = {
     "ddr_daily_objective_f32": (C.c_int, [C.POINTER(ObjectiveDesc), _P, _I64, _P, _I64, _P, _P, C.c_double, _P, _P, _P,
                                           _P, _P, _P]),
     "ddr_metrics_f32": (C.c_int, [_I64, _I64, _P, _I64, _P, _I64, _P, _P, _P]),
+    "ddr_summary_work_bytes": (_I64, [_I64, _I32, _I32]),
+    "ddr_summary_f32": (C.c_int, [_I64, _I64, _P, _I64, _I32, _P, _I32, _I32, _P, _P, _P]),
+    "ddr_summary_f64": (C.c_int, [_I64, _I64, _P, _I64, _I32, _P, _I32, _I32, _P, _P, _P]),
     "ddr_summedq_plan_create": (C.c_int, [_I64, _P, _P, _I64, _P, C.POINTER(C.c_void_p)]),
     "ddr_summedq_plan_destroy": (C.c_int, [_P]),
     "ddr_summedq_scratch_bytes": (_I64, [_P, _I64]),

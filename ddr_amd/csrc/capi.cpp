@@ -22,6 +22,7 @@
 #include "feed.h"
 #include "attrs.h"
 #include "period.h"
+#include "summary.h"
 
 namespace ddr {
 
@@ -711,6 +712,43 @@ ddr_status metrics_impl(int64_t n_gauges, int64_t n_days, const float* pred, int
                          static_cast<hipStream_t>(stream)));
   return DDR_OK;
 }
+static_assert(kSummaryTile == DDR_SUMMARY_TILE && kSummaryMaxQ == DDR_SUMMARY_MAX_Q, "summary.h and ddr_mc.h disagree");
+template <typename T>
+ddr_status summary_impl(int64_t R, int64_t N, const T* x, int64_t row_stride, int32_t K, const double* q,
+                        int32_t method, int32_t flags, double* out, void* work, void* stream) {
+  if (R < 0 || N < 0 || row_stride < 0 || K < 0) return fail(DDR_ERR_ARG, "summary: negative size");
+  if (K > kSummaryMaxQ)
+    return fail(DDR_ERR_ARG, "summary: at most " + std::to_string(kSummaryMaxQ) + " quantiles per call (got " +
+                                 std::to_string(K) + ")");
+  if (method < 0 || method >= DDR_N_SUMMARY_METHODS)
+    return fail(DDR_ERR_ARG, "summary: unknown method " + std::to_string(method));
+  if (flags & ~DDR_SUMMARY_SKIP_INF) return fail(DDR_ERR_ARG, "summary: unknown flag in " + std::to_string(flags));
+  if (K > 0 && !q) return fail(DDR_ERR_ARG, "summary: null q");
+  SummaryArgs a{};
+  for (int k = 0; k < K; ++k) {
+    if (!(q[k] >= 0.0 && q[k] <= 1.0))
+      return fail(DDR_ERR_ARG, "summary: q[" + std::to_string(k) + "] is outside [0, 1]");
+    a.q[k] = q[k];
+  }
+  if (R == 0) return DDR_OK;
+  if (N > INT32_MAX) return fail(DDR_ERR_ARG, "summary: N must be below 2^31");
+  if (R > kSummaryMaxRows) return fail(DDR_ERR_ARG, "summary: too many rows");
+  if (N > 0 && !x) return fail(DDR_ERR_ARG, "summary: null x");
+  if (!out) return fail(DDR_ERR_ARG, "summary: null out");
+  if (!work) return fail(DDR_ERR_ARG, "summary: null work (ddr_summary_work_bytes)");
+  if (reinterpret_cast<uintptr_t>(work) % 16) return fail(DDR_ERR_ARG, "summary: work must be 16-byte aligned");
+  a.x = x;
+  a.stride = row_stride;
+  a.R = R;
+  a.N = N;
+  a.K = K;
+  a.method = method;
+  a.flags = flags;
+  a.out = out;
+  a.work = work;
+  DDR_HIP(launch_summary<T>(a, static_cast<hipStream_t>(stream)));
+  return DDR_OK;
+}
 ddr_status daily_objective_impl(const ddr_objective_desc* desc, const float* daily, int64_t daily_stride,
                                 const float* obs, int64_t obs_stride, const uint8_t* drop, const float* weight,
                                 double count, const float* count_dev, float* loss, float* grad, double* terms,
@@ -1296,6 +1334,18 @@ ddr_status ddr_metrics_f32(int64_t n_gauges, int64_t n_days, const float* pred, 
                            const float* target, int64_t target_stride, double* out, int32_t* pred_nan_count,
                            void* stream) {
   DDR_GUARD({ return metrics_impl(n_gauges, n_days, pred, pred_stride, target, target_stride, out, pred_nan_count, stream); })
+}
+int64_t ddr_summary_work_bytes(int64_t R, int32_t K, int32_t elem_bytes) {
+  if (R < 0 || R > kSummaryMaxRows || K < 0 || K > kSummaryMaxQ || (elem_bytes != 4 && elem_bytes != 8)) return -1;
+  return (int64_t)summary_work_bytes(R, K, elem_bytes);
+}
+ddr_status ddr_summary_f32(int64_t R, int64_t N, const float* x, int64_t row_stride, int32_t K, const double* q,
+                           int32_t method, int32_t flags, double* out, void* work, void* stream) {
+  DDR_GUARD({ return summary_impl<float>(R, N, x, row_stride, K, q, method, flags, out, work, stream); })
+}
+ddr_status ddr_summary_f64(int64_t R, int64_t N, const double* x, int64_t row_stride, int32_t K, const double* q,
+                           int32_t method, int32_t flags, double* out, void* work, void* stream) {
+  DDR_GUARD({ return summary_impl<double>(R, N, x, row_stride, K, q, method, flags, out, work, stream); })
 }
 ddr_status ddr_summedq_plan_create(int64_t n_gauges, const int64_t* member_off, const int32_t* member_idx,
                                    int64_t chunk, void* stream, ddr_summedq_plan* plan) {

@@ -13,7 +13,11 @@ backward; the norm, the clip factor, the scaling; Adam's moment updates).  Here:
 * :class:`ClipAdam` -- clip + Adam over one flat parameter vector (``ddr_clip_adam_f32``), e.g.
   :class:`ddr_amd.pnet.ParamNet`'s ``flat``.
 
-Both are deterministic (fixed slices and reduction order) and run on the HIP device only.
+* :func:`step_summary` -- the step's log record (``scripts/train.py:110-132``): the means and medians over gauges of
+  NSE, RMSE and KGE and the min / median / max of the routing parameters, from :func:`ddr_amd.stats.summarize` calls
+  alone, read back with one small copy when a log line is due.
+
+All are deterministic (fixed slices and reduction order) and run on the HIP device only.
 """
 
 from __future__ import annotations
@@ -24,6 +28,8 @@ from dataclasses import dataclass
 import torch
 
 from . import _lib
+from .stats import SUMMARY_COLUMNS, summarize
+from .validation.metrics import METRIC_NAMES
 
 
 class _DailyL1(torch.autograd.Function):
@@ -203,3 +209,110 @@ class ClipAdam:
                                                  C.c_double(b2), C.c_float(self.eps), self.step_count.data_ptr(),
                                                  C.c_float(self.max_norm), self.last_norm.data_ptr(),
                                                  self.work.data_ptr(), _lib.stream_ptr(self.param.device)))
+
+
+_RULE = "-" * 40
+_COL = {name: k for k, name in enumerate(SUMMARY_COLUMNS + ("median",))}
+#: the rows of :attr:`StepSummary.record` before the parameters' rows
+STEP_METRICS = ("nse", "rmse", "kge")
+
+
+@dataclass
+class StepSummary:
+    """The log record of one step.  ``record`` is one (3 + P, 6) fp64 device tensor: rows ``nse, rmse, kge`` (over the
+    gauges; NSE without its NaN and +-inf entries) and one row per parameter in ``names`` order, columns ``count, min,
+    max, mean, std, median`` as :func:`ddr_amd.stats.summarize` wrote them.  ``sizes`` holds the parameters' lengths
+    (host integers: a NaN count is the length minus the count)."""
+
+    record: torch.Tensor
+    names: tuple
+    sizes: tuple
+
+    def read(self) -> dict:
+        """The single device-to-host copy.  Returns ``nse_mean, nse_median, rmse_mean, rmse_median, kge_mean,
+        kge_median`` and then, per parameter, ``{name}_min, {name}_median, {name}_max, {name}_nan_count``, in
+        this order (floats; the counts are ints)."""
+        return self.decode(self.record.cpu())
+
+    def decode(self, host) -> dict:
+        """:meth:`read`'s dict from a host copy of ``record`` (a (3 + P, 6) tensor, array or nested list)."""
+        rows = [[float(v) for v in row] for row in (host.tolist() if hasattr(host, "tolist") else host)]
+        if len(rows) != len(STEP_METRICS) + len(self.names) or any(len(r) != len(_COL) for r in rows):
+            raise ValueError(f"the record must be ({len(STEP_METRICS) + len(self.names)}, {len(_COL)})")
+        out = {}
+        for k, m in enumerate(STEP_METRICS):
+            out[f"{m}_mean"] = rows[k][_COL["mean"]]
+            out[f"{m}_median"] = rows[k][_COL["median"]]
+        for k, (name, size) in enumerate(zip(self.names, self.sizes)):
+            row = rows[len(STEP_METRICS) + k]
+            out[f"{name}_min"] = row[_COL["min"]]
+            out[f"{name}_median"] = row[_COL["median"]]
+            out[f"{name}_max"] = row[_COL["max"]]
+            out[f"{name}_nan_count"] = int(size) - int(row[_COL["count"]])
+        return out
+
+    def lines(self, epoch: int | None = None, mini_batch: int | None = None, values: dict | None = None) -> list:
+        """The reference's log lines for this step: ``utils.log_metrics``' table (``validation/utils.py:104-113``) and
+        one ``"{name}: min=..., median=..., max=..."`` line per parameter (``scripts/train.py:128-132``), with the
+        same format strings; the caller logs them.  ``values`` is :meth:`read`'s dict (read now when not given).
+        A parameter that holds NaN gets `` (nan_count=k)`` appended: its NaN are counted, not propagated."""
+        v = self.read() if values is None else values
+        out = []
+        if epoch is not None and mini_batch is not None:
+            out += [_RULE, f"Epoch: {epoch:<9} | Mini Batch: {mini_batch:<8} "]
+        out += [_RULE, f"{'Metric':<10} | {'Mean':>12} | {'Median':>12}", _RULE]
+        for m in STEP_METRICS:
+            out.append(f"{m.upper():<10} | {v[f'{m}_mean']:12.4f} | {v[f'{m}_median']:12.4f}")
+        out.append(_RULE)
+        for name in self.names:
+            line = (f"{name}: min={v[f'{name}_min']:.6f}, median={v[f'{name}_median']:.6f}, "
+                    f"max={v[f'{name}_max']:.6f}")
+            if v[f"{name}_nan_count"]:
+                line += f" (nan_count={v[f'{name}_nan_count']})"
+            out.append(line)
+        return out
+
+
+def step_summary(metric_values: torch.Tensor, params, *, out: torch.Tensor | None = None) -> StepSummary:
+    """The step's log record on the device, replacing ``scripts/train.py:110-132``'s host work (``nanmean`` /
+    ``nanmedian`` over gauges, and per parameter a ``.cpu()`` with ``min / median / max``).
+
+    ``metric_values`` is :func:`ddr_amd.validation.metrics_device`'s (18, G) fp64 tensor; ``params`` an ordered
+    mapping of name -> (N,) fp32 tensor (``routing_model.n / q_spatial / p_spatial``).  Only
+    :func:`~ddr_amd.stats.summarize` calls are issued, each writing its rows of the record in place: the NSE row
+    with ``skip_inf`` (the reference drops its NaN and +-inf entries), the RMSE and KGE rows as one strided view,
+    and one call per parameter with the ``lower`` median (``torch.median``'s element).  No host sync: a captured
+    step can hold it, with ``out`` a fixed contiguous (3 + P, 6) fp64 tensor.
+
+    One deviation: the reference's ``torch.min / median / max`` propagate a NaN in a parameter; here NaN are left
+    out and counted (``{name}_nan_count``)."""
+    if not isinstance(metric_values, torch.Tensor):
+        raise TypeError("step_summary takes metrics_device's tensor")
+    if metric_values.dtype != torch.float64 or metric_values.dim() != 2 or metric_values.shape[0] != len(METRIC_NAMES):
+        raise ValueError(f"metric_values must be the ({len(METRIC_NAMES)}, G) float64 tensor of metrics_device")
+    if not hasattr(params, "items"):
+        raise ValueError("params must be a mapping of name -> (N,) float32 tensor")
+    items = [(str(k), v) for k, v in params.items()]
+    for name, t in items:
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.dim() != 1:
+            raise ValueError(f"parameter {name!r} must be a (N,) float32 tensor")
+        if t.device != metric_values.device:
+            raise ValueError(f"parameter {name!r} must be on metric_values' device")
+    rows = len(STEP_METRICS) + len(items)
+    if out is not None and (not isinstance(out, torch.Tensor) or out.dtype != torch.float64
+                            or out.shape != (rows, len(_COL)) or not out.is_contiguous()
+                            or out.device != metric_values.device):
+        raise ValueError(f"out must be a contiguous ({rows}, {len(_COL)}) float64 tensor on metric_values' device")
+    if not metric_values.is_cuda:
+        raise RuntimeError("step_summary runs on the HIP device only (no CPU fallback)")
+    mv = metric_values.detach()
+    if mv.shape[1] > 1 and mv.stride(1) != 1:
+        mv = mv.contiguous()
+    i_nse, i_rmse, i_kge = (METRIC_NAMES.index(m) for m in STEP_METRICS)
+    with torch.cuda.device(mv.device):
+        rec = out if out is not None else torch.empty((rows, len(_COL)), device=mv.device, dtype=torch.float64)
+        summarize(mv[i_nse], q=(0.5,), skip_inf=True, out=rec[0:1])
+        summarize(mv[i_rmse::i_kge - i_rmse][:2], q=(0.5,), out=rec[1:3])
+        for k, (_, t) in enumerate(items):
+            summarize(t, q=(0.5,), method="lower", out=rec[3 + k:4 + k])
+    return StepSummary(rec, tuple(n for n, _ in items), tuple(int(t.numel()) for _, t in items))

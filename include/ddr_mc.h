@@ -566,6 +566,35 @@ ddr_status ddr_metrics_f32(int64_t n_gauges, int64_t n_days, const float* pred, 
                            const float* target, int64_t target_stride, double* out, int32_t* pred_nan_count,
                            void* stream);
 
+/* NaN-aware summaries of long rows (numpy's nanmin / nanmax / nanmean / nanstd / nanquantile: the attribute
+ * statistics of src/ddr/io/statistics.py:45-52, the medians of src/ddr/validation/utils.py:110-112 and of
+ * scripts/train.py:127-131), exact, with no host sync, no allocation and no copy: the call can be captured.
+ *   x       device fp32 (ddr_summary_f32) or fp64 (ddr_summary_f64), row r at x + r * row_stride (in elements),
+ *           0 <= N < 2^31 values each.  NaN never takes part; with DDR_SUMMARY_SKIP_INF neither does +-inf.
+ *   q       host array of K <= DDR_SUMMARY_MAX_Q probabilities in [0, 1]; they travel as kernel arguments.
+ *   method  DDR_SUMMARY_LINEAR: numpy's default.  With n the row's count and v = (n - 1) q in fp64, lo = floor(v),
+ *           g = v - lo, a and b the order statistics lo and min(lo + 1, n - 1): a + (b - a) g, and
+ *           b - (b - a) (1 - g) when g >= 0.5, each operation rounded on its own.
+ *           DDR_SUMMARY_LOWER: the order statistic floor(v); q = 0.5 is torch.median's element (n - 1) / 2.
+ *   out     device fp64 (R, DDR_SUMMARY_N_COLUMNS + K): the DDR_SUMMARY_* columns below, then the K quantiles.
+ *           std is the population's (ddof = 0), two-pass: sqrt(sum (x - mean)^2 / count).  A row without a counted
+ *           value gets count 0 and NaN in every other column.  The order statistics are selected through
+ *           most-significant-digit radix histograms over order-preserving keys (nothing is sorted); the moments are
+ *           fp64 sums in a fixed order: a row's record does not depend on R or on the row's position.
+ *   work    device scratch of ddr_summary_work_bytes(R, K, sizeof element) bytes, 16-byte aligned.
+ * Rows are walked DDR_SUMMARY_TILE elements per workgroup at a time.  R == 0 is a no-op; N == 0 writes the record of
+ * an empty row.  ddr_summary_work_bytes returns -1 for arguments the calls would refuse. */
+enum { DDR_SUMMARY_COUNT = 0, DDR_SUMMARY_MIN, DDR_SUMMARY_MAX, DDR_SUMMARY_MEAN, DDR_SUMMARY_STD, DDR_SUMMARY_N_COLUMNS };
+enum { DDR_SUMMARY_LINEAR = 0, DDR_SUMMARY_LOWER, DDR_N_SUMMARY_METHODS };
+#define DDR_SUMMARY_SKIP_INF 1
+#define DDR_SUMMARY_MAX_Q 8
+#define DDR_SUMMARY_TILE 4096
+int64_t ddr_summary_work_bytes(int64_t R, int32_t K, int32_t elem_bytes);
+ddr_status ddr_summary_f32(int64_t R, int64_t N, const float* x, int64_t row_stride, int32_t K, const double* q,
+                           int32_t method, int32_t flags, double* out, void* work, void* stream);
+ddr_status ddr_summary_f64(int64_t R, int64_t N, const double* x, int64_t row_stride, int32_t K, const double* q,
+                           int32_t method, int32_t flags, double* out, void* work, void* stream);
+
 /* The summed-Q' baseline of the evaluation (scripts/summed_q_prime.py:208-261, eval_q_prime): per gauge and day
  * the sum of the lateral inflow of the gauge's upstream divides, the unrouted series that routed results are
  * scored against.  With rho = hours_per_step (24: hourly store, 1: daily store) and D = n_steps / rho (trailing
