@@ -91,7 +91,7 @@ struct PendingStatus {
       snprintf(id, sizeof(id), " (graph %p, stream %p, routing launch #%llu of this process)", graph[k],
                (void*)stream[k], seq[k]);
       // word 1: first failing logical block + 1, or 0x40000000 + rank for a split basin's peer that never
-      // arrived at the launch's epoch hand-shake (route.hip: split_barrier_kernel)
+      // arrived at the launch's epoch hand-shake (split.hip: split_barrier_kernel)
       const std::string where = w[1] >= 0x40000000u
                                     ? "split-basin hand-shake: rank " + std::to_string((int)(w[1] - 0x40000000u)) +
                                           " never arrived"
@@ -279,11 +279,11 @@ void fill_common(RouteArgs& a, const Graph* g, const ddr_mc_consts* c, const ddr
   a.ln_dlb = std::log(sizeof(R) == 4 ? (double)a.cf[4] : a.c[4]);
 }
 
-// The routing kernels need no co-residency (ticket-ordered blocks, route.hip), only that one
+// The routing kernels need no co-residency (ticket-ordered blocks, route_device.h), only that one
 // workgroup fits a CU with the schedule's LDS.
 template <typename R>
 ddr_status check_launchable(const Graph* g, bool backward) {
-  const int cap = max_resident_blocks<R>(g, backward);
+  const int cap = backward ? backward_resident_blocks<R>(g) : forward_resident_blocks<R>(g);
   if (cap < 0) return fail(DDR_ERR_HIP, "occupancy query failed");
   if (cap == 0)
     return fail(DDR_ERR_CAPACITY, std::string("the ") + (backward ? "backward" : "forward") +
@@ -374,7 +374,7 @@ ddr_status forward_impl(const ddr_graph* gh, const ddr_mc_consts* c, const ddr_m
   DDR_HIP(launch_gather_qprime<R>(g, a, s));
   if (flags & DDR_FWD_CHECK_QPRIME) DDR_HIP(nan_check_mark(status, s));
   DDR_HIP(timing_mark(0, 0, s));
-  DDR_HIP(launch_route<R>(g, a, false, s));
+  DDR_HIP(launch_route_forward<R>(g, a, s));
   DDR_HIP(timing_mark(0, 1, s));
   DDR_HIP(launch_split_finish<R>(g, a, s));
   // runoff (N, T) is written by the routing kernel itself (16-B row segments every 4 steps)
@@ -455,7 +455,7 @@ ddr_status backward_impl(const ddr_graph* gh, const ddr_mc_consts* c, const ddr_
   }
   if ((st = split_prepare(g, a, T, 1, s))) return st;
   DDR_HIP(timing_mark(1, 0, s));
-  DDR_HIP(launch_route<R>(g, a, true, s));
+  DDR_HIP(launch_route_backward<R>(g, a, s));
   DDR_HIP(timing_mark(1, 1, s));
   if (gqp) DDR_HIP(launch_scatter_qprime_grad<R>(g, a, qp_rows, gqp, s));
   return cap ? DDR_OK : g_pending.enqueue(status, s, "backward", gh);
@@ -1712,8 +1712,8 @@ const char* ddr_last_error(void) { return ddr::last_error_cstr(); }
 #ifndef DDR_SOURCE_HASH
 #define DDR_SOURCE_HASH "unknown"
 #endif
-// src: every library source; kern: the routing kernels' sources only (route.hip and the headers it
-// includes) -- the key of the PMC counter files under profiles/counters (bench.py), which describe the
+// src: every library source; kern: the routing kernels' sources only (the Makefile's KERN_SRCS: the routing units and
+// the headers they include) -- the key of the PMC counter files under profiles/counters (bench.py), which describe the
 // kernels and stay valid across host-side changes.  The kernel hash is the last word.
 #ifndef DDR_KERNEL_HASH
 #define DDR_KERNEL_HASH "unknown"

@@ -755,7 +755,7 @@ __global__ void k_emit_up(int64_t n, const int32_t* order, const int32_t* blk, c
     uplist[u0 + (k - k0)] = u;
   }
   if (nx[P]) {
-    // confluence list: [c, u1, ..., u_{c-1}] (route.hip pack_up)
+    // confluence list: [c, u1, ..., u_{c-1}] (route_device.h pack_up)
     const int32_t x = xbase[P];
     xlist[x] = k1 - k0;
     for (int32_t k = 1; k < k1 - k0; ++k) xlist[x + k] = uplist[u0 + k];

@@ -211,7 +211,7 @@ ddr_status plan_init(int64_t n, int64_t bmax, const ddr_build_opts* opts, PackPl
 }
 
 // ---- packing of the pieces into workgroups ----------------------------------------------------
-// Workgroups take their logical block index from a ticket counter in block order (route.hip:
+// Workgroups take their logical block index from a ticket counter in block order (route_device.h:
 // take_ticket), and blocks are numbered by piece height, so a running workgroup's producers are
 // running or done: a schedule with more blocks than resident workgroups is still deadlock-free.
 // The packer first tries to fit one resident generation (all blocks co-resident, fully time-
@@ -268,7 +268,7 @@ ddr_status pack_pieces(PackPlan& P, const PieceTable& pt, PackResult& R, int* ou
   const double capw0 = wsum / (double)limit;
   // light loads (capacity <= half a workgroup, one reach per thread): no block above half a workgroup while
   // the capacity stays there -- a block of 513+ reaches has no idle upper waves (storer / import / x-helper
-  // waves, route.hip) and three routing waves per SIMD, and sets the kernel's pace (a C3 8-way shard's
+  // waves, route_forward.hip) and three routing waves per SIMD, and sets the kernel's pace (a C3 8-way shard's
   // five 700-reach blocks: 8.15 ms against 6.9-7.5 for the shards without); the capacity growth below
   // lifts the clamp when the blocks do not fit otherwise
   const bool light_clamp = !getenv("DDR_PACK_NO_LIGHT_CLAMP") && P.cap <= kBlockThreads / 2;
@@ -658,7 +658,7 @@ ddr_status build_graph(int64_t n, int64_t e, const int32_t* rows, const int32_t*
   }
   // Cut edges are numbered in (block, local position) order, i.e. by their index in cout_loc: the
   // forward kernel derives a cut reach's granule row from B.cout0 + its rank among the block's
-  // cut reaches (route.hip), with no table load in the tick.
+  // cut reaches (route_forward.hip), with no table load in the tick.
   int64_t eid = 0;
   for (int64_t P = 0; P < n; ++P) {
     const int32_t i = order_all[P];
@@ -686,7 +686,7 @@ ddr_status build_graph(int64_t n, int64_t e, const int32_t* rows, const int32_t*
         }
       }
       if (upc[P] > 2) {
-        // confluence list: [c, u1, ..., u_{c-1}] at xoff (block-local), see route.hip pack_up
+        // confluence list: [c, u1, ..., u_{c-1}] at xoff (block-local), see route_device.h pack_up
         xoff[P] = (int32_t)(xlist.size() - B.xl0);
         xlist.push_back(upc[P]);
         for (int32_t k = 1; k < upc[P]; ++k) xlist.push_back(uplist[upb[P] + k]);

@@ -1,5 +1,5 @@
 // Internal definitions shared by the host graph builder (graph.cpp), the routing kernels
-// (route.hip) and the C ABI (capi.cpp).  Not part of the public interface (include/ddr_mc.h).
+// (route_forward.hip, route_backward.h) and the C ABI (capi.cpp).  Not part of the public interface (include/ddr_mc.h).
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -69,7 +69,7 @@ inline int kr_of_load(int64_t max_load) {
   while (int64_t(kr) * kBlockThreads < max_load) kr *= 2;
   return kr;
 }
-// Dynamic LDS of the routing kernels (route.hip), for `slots` = nloc + nvirt slots and `nring`
+// Dynamic LDS of the routing kernels (route_forward.hip, route_backward.h), for `slots` = nloc + nvirt slots and `nring`
 // import rings (virtual inflows forward, cut-outs backward), reals of `rsize` bytes:
 //   forward : x slots (f64, xbuf buffers) | 6 statics (R) | ring [nvirt][kChunkFwd] f64
 //   backward: A slots (R) | B slots (R) | published x slots (R) (each xbuf buffers) | 6 statics (R)
@@ -304,7 +304,7 @@ ddr_status upload_schedule_async(Graph* g, hipStream_t stream);
 
 // Status block layout (device, zeroed before every launch): word 0 = timed-out hand-offs, word 1 =
 // first failing block + 1, word 2 = forward ticket counter, word 3 = backward ticket counter.
-// Workgroups take their logical block from the ticket counter (route.hip: take_ticket), so a
+// Workgroups take their logical block from the ticket counter (route_device.h: take_ticket), so a
 // running workgroup's producers are always running or finished: any grid size is deadlock-free.
 constexpr int64_t kStatusBytes = 256;
 constexpr int kStatusTicketFwd = 2;

@@ -18,7 +18,7 @@ struct PeriodArgs {
 // the days [d_lo, d_lo + nd) of (0 <= d < D) whose window meets [h0, h0 + T); nd = 0: none
 void period_days(int64_t T, int64_t D, int64_t h0, int64_t first_hour, int64_t* d_lo, int32_t* nd);
 
-// gauge rows: the gauge sums of gauge_reduce_kernel (route.hip), `a` from gauge_args (capi.cpp)
+// gauge rows: the gauge sums of gauge_reduce_kernel (gauges.hip), `a` from gauge_args (capi.cpp)
 template <typename R>
 hipError_t launch_period_gauge(const GaugeArgs& a, const PeriodArgs& p, const R* xsave, R* daily, hipStream_t stream);
 // every reach in reference order: the value the forward's (N, T) runoff holds.  direct: one thread per

@@ -12,9 +12,10 @@
 // bit-identical whatever the chunking, no atomics, no clearing (days no call touches are not written).
 //
 // The hourly value is what the hourly paths give for the same launch: the gauge sum of gauge_reduce_kernel
-// (route.hip; restated here), or in all-reach mode max(x, q_lb), the forward's (N, T) runoff entry.
+// (gauge_hour, gauge_sum.h), or in all-reach mode max(x, q_lb), the forward's (N, T) runoff entry.
 #include "period.h"
 
+#include "gauge_sum.h"
 #include "internal.h"
 #include "physics.h"
 
@@ -38,22 +39,6 @@ __device__ __forceinline__ DaySpan span_of(const PeriodArgs& p, int64_t d) {
   const int64_t lo = w0 > p.h0 ? w0 : p.h0;
   const int64_t hi = w1 < p.h0 + p.T ? w1 : p.h0 + p.T;
   return {lo - p.h0, hi - p.h0, lo == w0, hi == w1};
-}
-
-// the hourly gauge value, as gauge_hour / gauge_reduce_kernel (route.hip): the sum of the members' clamped
-// states, the carried state of step 0 unclamped, and the sum of step 0 clamped (mmc.py:412, 433-439)
-template <typename R>
-__device__ __forceinline__ R gauge_hour(const GaugeArgs& a, const R* xsave, int64_t g, int64_t t) {
-  R acc = R(0);
-  for (int64_t k = a.goff[g]; k < a.goff[g + 1]; ++k) {
-    const int P = a.pos_of_ref[a.gidx[k]];
-    const BlockDesc B = a.s.blocks[a.block_of_pos[P]];
-    const int r = P - B.pos0;
-    const int64_t tick = t + a.s.off[P];
-    const R x = xsave[a.T * B.pos0 + B.pre_dn + tick * B.nloc + r];
-    acc = acc + ((t == 0 && a.carry) ? x : rmax_nan(x, R(a.qlb)));
-  }
-  return (t == 0) ? rmax_nan(acc, R(a.qlb)) : acc;
 }
 
 // Gauge rows: 32 lanes per (gauge, day of this launch).  Lane k takes the window's hour k -- the hourly values are
@@ -81,7 +66,7 @@ __global__ void __launch_bounds__(256) period_gauge_kernel(GaugeArgs a, PeriodAr
   if (live && lane == 0) *out = sp.last ? sum / R(24) : sum;
 }
 
-// a reach's column of the schedule-layout x_save (state_at_kernel's access, route.hip): step t at xs[t * nloc]
+// a reach's column of the schedule-layout x_save (state_at_kernel's access, gauges.hip): step t at xs[t * nloc]
 template <typename R>
 struct ReachColumn {
   const R* xs;

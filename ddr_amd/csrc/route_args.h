@@ -1,4 +1,5 @@
-// Kernel argument blocks and launchers shared by route.hip and capi.cpp.
+// Kernel argument blocks and launchers shared by the routing units (route_forward.hip, route_backward.h,
+// qprime.hip, gauges.hip, split.hip) and capi.cpp.
 #pragma once
 
 #include "internal.h"
@@ -88,13 +89,21 @@ struct GaugeArgs {
   int32_t carry;
 };
 
+// the fused routing launches (route_forward.hip, route_backward.h) and the workgroups of each that the
+// device holds at this schedule's LDS size (0: one does not fit a CU; -1: the query failed)
 template <typename R>
-hipError_t launch_route(const Graph* g, const RouteArgs& a, bool backward, hipStream_t stream);
-// Q(t) of every reach (reference order) from a forward's saved states (route.hip: state_at_kernel)
+hipError_t launch_route_forward(const Graph* g, const RouteArgs& a, hipStream_t stream);
+template <typename R>
+hipError_t launch_route_backward(const Graph* g, const RouteArgs& a, hipStream_t stream);
+template <typename R>
+int forward_resident_blocks(const Graph* g);
+template <typename R>
+int backward_resident_blocks(const Graph* g);
+// Q(t) of every reach (reference order) from a forward's saved states (gauges.hip: state_at_kernel)
 template <typename R>
 hipError_t launch_state_at(const Graph* g, int64_t T, int64_t t, double qlb, bool carry, const R* xsave, R* out,
                            hipStream_t stream);
-// split basin: the epoch hand-shake before a routing launch (route.hip: split_barrier_kernel)
+// split basin: the epoch hand-shake before a routing launch (split.hip: split_barrier_kernel)
 struct SplitBarrierArgs {
   unsigned long long* mine;                  // this rank's epoch words ([2][kMaxSplitRanks])
   unsigned long long* peer[kMaxSplitRanks];  // every rank's epoch words
@@ -115,8 +124,6 @@ hipError_t launch_scatter_qprime_grad(const Graph* g, const RouteArgs& a, int64_
 // per-gauge clamp mask of the t = 0 gauge sum (mmc.py:398-412), for the state-gradient backward
 template <typename R>
 hipError_t launch_gauge_mask0(const GaugeArgs& a, const R* xsave, unsigned char* mask, hipStream_t stream);
-template <typename R>
-int max_resident_blocks(const Graph* g, bool backward);
 template <typename R>
 hipError_t launch_gather_qprime(const Graph* g, RouteArgs& a, hipStream_t stream);
 // Sets a.qs_rows / a.qp_magic when the window's q' store has several steps per row and the

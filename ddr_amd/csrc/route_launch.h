@@ -1,0 +1,60 @@
+// Host side of a routing launch, shared by route_forward.hip and route_backward.h: the dynamic-LDS
+// plan (one definition for the launches, the backward's buffer choice and the occupancy queries) and
+// the launch geometry.
+#pragma once
+
+#include <algorithm>
+
+#include "internal.h"
+#include "route_args.h"
+
+namespace ddr {
+
+// Split basin: after the layout, each block's granule rows (tagged pointers, bit 0 = another rank's
+// memory: system scope): forward, its cut-outs' export rows; backward, its virtuals' export rows then
+// its cut-outs' import rows -- resolved once per launch, no dependent global load per hand-off
+inline size_t split_table_bytes(const Graph* g, bool backward) {
+  if (g->split.nranks == 0) return 0;
+  return 8 * (size_t)(backward ? g->max_virt + g->max_cout : g->max_cout);
+}
+
+// Dynamic LDS of a routing launch on this graph (route_lds_bytes, internal.h): `base` bytes of layout
+// closed by the confluence lists, then the split basin's row table; `smem` in all.  The offsets are the
+// kernels' RouteArgs fields of the same names.
+struct RouteLds {
+  size_t base, smem;
+  int32_t xl_off, own_off, xt_off;
+};
+// xb: the slot buffers when not the KR rule's (0), as route_lds_bytes
+template <typename R>
+RouteLds route_lds_plan(const Graph* g, bool backward, int xb) {
+  RouteLds p;
+  p.base = route_lds_bytes((size_t)route_slot_stride(g->max_slots), (size_t)g->max_virt, (size_t)g->max_cout,
+                           (size_t)g->max_xl, backward, sizeof(R), g->kr, xb);
+  p.smem = align16(p.base) + split_table_bytes(g, backward);
+  p.xl_off = (int32_t)(p.base - (size_t)g->max_xl * 4);  // the lists close the base LDS layout
+  p.own_off = p.xl_off - (int32_t)align16(4 * (size_t)std::max(g->max_virt, g->max_cout));
+  p.xt_off = g->split.nranks > 0 ? (int32_t)align16(p.base) : 0;
+  return p;
+}
+
+// The launch arguments that follow from the graph and the plan
+inline void set_launch_args(RouteArgs& a, const Graph* g, const RouteLds& p) {
+  a.slot_stride = route_slot_stride(g->max_slots);
+  a.n_cut = g->n_cut;
+  a.nblocks = (int32_t)g->blocks.size();
+  a.xl_off = p.xl_off;
+  a.own_off = p.own_off;
+  a.xt_off = p.xt_off;
+}
+
+// Workgroups of kernel `f` resident on the device with `smem` bytes of dynamic LDS each (-1: query failed)
+inline int resident_blocks(const Graph* g, const void* f, size_t smem) {
+  int nb = 0;
+  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, f, kBlockThreads, smem) != hipSuccess) return -1;
+  hipDeviceProp_t prop;
+  if (hipGetDeviceProperties(&prop, g->device) != hipSuccess) return -1;
+  return nb * prop.multiProcessorCount;
+}
+
+}  // namespace ddr

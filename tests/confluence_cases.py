@@ -2,7 +2,7 @@
 two inflows, and a classifier of what a built graph made of them.
 
 ``ddr_amd.synthetic`` caps the in-degree at 2 (``random_binary_tree`` by construction, ``hack_basin`` with one
-tributary per spine joint), so none of its networks reaches the routing kernels' confluence list (csrc/route.hip
+tributary per spine joint), so none of its networks reaches the routing kernels' confluence list (csrc/route_device.h
 ``pack_up`` / ``up_1`` and the ``j = 2..c`` tails; csrc/graph.cpp and csrc/devgraph.hip ``xoff`` / ``xlist``).  Real
 MERIT and Lynker networks do.  The builders here are deterministic, numbered upstream first, and return
 ``synthetic.SyntheticNetwork`` with the COO of ``synthetic._down_to_coo``.

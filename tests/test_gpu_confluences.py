@@ -1,6 +1,6 @@
 """The routing kernels and both graph builders on reaches with more than two inflows.
 
-Every other network of the suite has in-degree <= 2, so none reaches the kernels' confluence list (csrc/route.hip
+Every other network of the suite has in-degree <= 2, so none reaches the kernels' confluence list (csrc/route_device.h
 ``pack_up`` / ``up_1``, the ``j = 2..c`` tails of the forward tick, the backward recompute and its prologue,
 ``load_xlist``) or its emission (csrc/graph.cpp, csrc/devgraph.hip ``xoff`` / ``xlist``).  The networks are those of
 tests/confluence_cases.py; tests/test_confluence_cases.py asserts on the CPU that each (network, partition) used

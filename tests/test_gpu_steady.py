@@ -90,7 +90,7 @@ def test_storer_waves_are_bitwise_the_compute_wave_stores(cuda, T):
 @pytest.mark.parametrize("cap", [256, 1536, 4096], ids=["kr1", "kr2", "kr4"])
 def test_plain_instances_are_bitwise_the_general_ones(cuda, cap):
     """Launches without the rare options (split basin, block profile, state seeds, daily accumulation) run
-    kernel instances compiled without them (route.hip, PL); outputs and gradients equal the general
+    kernel instances compiled without them (route_forward.hip, route_backward.h, PL); outputs and gradients equal the general
     instances' (DDR_DEBUG_NO_PLAIN) bit for bit, per-reach runoff and gauge mode, at one, two and four reaches
     per thread."""
     net = synthetic.forest(synthetic.loguniform_sizes(10, 200, 12000, 13), seed=13)

@@ -116,7 +116,7 @@ def test_partition_invariants(cap):
             if indeg[w] == 0:
                 stack.append(w)
     assert seen == len(counts), "block dependency graph has a cycle"
-    # ticket order (route.hip take_ticket): every producer block precedes its consumers
+    # ticket order (route_device.h take_ticket): every producer block precedes its consumers
     assert all(a < b for a, b in edges), "a cut edge runs from a later block to an earlier one"
     # save buffer sizes
     assert g.save_numel(10) == 2 * net.n * 10 + g.info.save_elems_fixed
@@ -197,7 +197,7 @@ def test_generation_fallback_builds_fast():
 
 def test_light_load_blocks_keep_half_a_workgroup(monkeypatch):
     """At light load (block capacity <= 512 reaches, one per thread) no block exceeds 512 reaches: a larger
-    one loses the idle helper waves and runs three routing waves per SIMD (route.hip).  C3 8-way shard 3
+    one loses the idle helper waves and runs three routing waves per SIMD (route_forward.hip).  C3 8-way shard 3
     packed five ~700-reach blocks before the rule (graph.cpp light_clamp; profiles/r04/ab_r04.txt item 24);
     DDR_PACK_NO_LIGHT_CLAMP restores the previous packing, which the last assertion checks is still the
     case that needs the rule."""

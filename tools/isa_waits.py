@@ -2,8 +2,8 @@
 
     python tools/isa_waits.py [forward|backward] [KR] [extra -D flags ...]
 
-Compiles route.hip for gfx950 (device only, -S) with -DDDR_PHASE_PROF=1 and prints, between
-consecutive s_memtime markers, every s_waitcnt that includes vmcnt with the two preceding
+Compiles route_forward.hip or route_backward_f32.hip for gfx950 (device only, -S) with -DDDR_PHASE_PROF=1
+and prints, between consecutive s_memtime markers, every s_waitcnt that includes vmcnt with the two preceding
 instructions, so a wait that would drain the tick's prefetches stands out.
 """
 import re
@@ -15,10 +15,11 @@ kind = sys.argv[1] if len(sys.argv) > 1 else "forward"
 kr = sys.argv[2] if len(sys.argv) > 2 else "4"
 extra = sys.argv[3:]
 src = Path(__file__).resolve().parents[1] / "ddr_amd" / "csrc"
+unit = "route_forward.hip" if kind == "forward" else "route_backward_f32.hip"  # the fp32 instances
 out = Path("/tmp/isa_waits.s")
 cmd = ["/opt/rocm/bin/hipcc", "-O3", "-std=c++17", "--offload-arch=gfx950", "-ffp-contract=off",
        "-fhip-fp32-correctly-rounded-divide-sqrt", "-Wno-unused-function", "-DDDR_PHASE_PROF=1", *extra, "-x", "hip",
-       "--cuda-device-only", "-S", str(src / "route.hip"), "-o", str(out)]
+       "--cuda-device-only", "-S", str(src / unit), "-o", str(out)]
 subprocess.run(cmd, check=True, stderr=subprocess.DEVNULL)
 s = out.read_text()
 name = re.findall(rf"^(_Z\w*route_{kind}_kernelIfLi{kr}\w*):", s, re.M)[0]
