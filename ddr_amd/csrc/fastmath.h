@@ -13,7 +13,10 @@
 //   the correctly rounded value in ~1.7% of cases; the oracle uses the correctly rounded value.
 // div_rn(a, b): IEEE round-to-nearest quotient for normal operands whose quotient is normal (no
 //   scaling steps): refined reciprocal + one FMA residual correction (Markstein).
-// Both are checked on the GPU against fp64 references by tools/fm_check.hip.
+// Both are checked on the GPU against fp64 references by tools/fm_check.hip (stand-alone, against the device's own
+// pow), and in the suite by tests/test_gpu_physics_box.py: the physics built on them, bit for bit against the fp32
+// oracle over the configuration's parameter box, with the table and exponent boundaries of ln_tab as edge planes;
+// tests/test_physics_box.py checks the tables of mathtab.h against mpmath and the generator.
 #pragma once
 
 #include <hip/hip_runtime.h>
