@@ -25,4 +25,8 @@ def __getattr__(name):
         from . import inference
 
         return getattr(inference, name)
+    if name == "Network":
+        from .network import Network
+
+        return Network
     raise AttributeError(name)

@@ -34,6 +34,7 @@ DDR_BUILD_HOST_ONLY = 1
 
 DDR_UPSTREAM_HOST_ONLY = 1
 DDR_UPSTREAM_DEVICE_COO = 2
+DDR_NETWORK_DEVICE_INPUT = 1
 
 DDR_FWD_SAVE_X = 1
 DDR_FWD_CARRY = 2
@@ -86,6 +87,10 @@ class KanDesc(C.Structure):
 
 class UpstreamInfo(C.Structure):
     _fields_ = [(name, C.c_int64) for name in ("n", "n_outlets", "max_depth", "rounds", "device")]
+
+
+class NetworkCounts(C.Structure):
+    _fields_ = [(name, C.c_int64) for name in ("n", "kept", "nnz", "n_dropped", "n_basins", "max_depth", "device")]
 
 
 class GeomSlot(C.Structure):
@@ -201,6 +206,13 @@ _SIGS = {
                                             C.POINTER(C.c_int64), _P, _P, _I64, _P]),
     "ddr_upstream_member_counts_host": (C.c_int, [_P, _I64, _P, _P]),
     "ddr_upstream_members_host": (C.c_int, [_P, _I64, _P, _P, _P]),
+    "ddr_network_build": (C.c_int, [_I64, _P, _P, _I32, _P, C.POINTER(C.c_void_p)]),
+    "ddr_network_build_host": (C.c_int, [_I64, _P, _P, C.POINTER(C.c_void_p)]),
+    "ddr_network_info": (C.c_int, [_P, C.POINTER(NetworkCounts)]),
+    "ddr_network_get": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _P]),
+    "ddr_network_destroy": (C.c_int, [_P]),
+    "ddr_network_lookup_i64": (C.c_int, [_I64, _P, _I64, _P, _P, _I32, _P]),
+    "ddr_network_lookup_i64_host": (C.c_int, [_I64, _P, _I64, _P, _P]),
     "ddr_attr_prepare_f32": (C.c_int, [_I64, _I32, _P, _I64, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "ddr_geometry_predict_f32": (C.c_int, [_I64, _I32, _P, C.POINTER(GeomSlot), C.POINTER(GeomSlot),
                                            C.POINTER(GeomSlot), _P, _P, C.c_double, C.c_double, C.c_double,

@@ -18,6 +18,7 @@
 #include "geopredict.h"
 #include "summedq.h"
 #include "bmi.h"
+#include "network.h"
 #include "upstream.h"
 #include "feed.h"
 #include "attrs.h"
@@ -1495,6 +1496,47 @@ ddr_status ddr_upstream_member_counts_host(ddr_upstream_index index, int64_t n_g
 ddr_status ddr_upstream_members_host(ddr_upstream_index index, int64_t n_gauges, const int32_t* gage_idx,
                                      const int64_t* off, int32_t* idx) {
   DDR_GUARD({ return upstream_members_host(static_cast<const UpstreamIndex*>(index), n_gauges, gage_idx, off, idx); })
+}
+ddr_status ddr_network_build(int64_t n, const int64_t* ids, const int64_t* to_ids, int32_t flags, void* stream,
+                             ddr_network* network) {
+  DDR_GUARD({
+    return network_build(n, ids, to_ids, flags, static_cast<hipStream_t>(stream),
+                         reinterpret_cast<Network**>(network));
+  })
+}
+ddr_status ddr_network_build_host(int64_t n, const int64_t* ids, const int64_t* to_ids, ddr_network* network) {
+  DDR_GUARD({ return network_build_host(n, ids, to_ids, reinterpret_cast<Network**>(network)); })
+}
+ddr_status ddr_network_info(ddr_network network, ddr_network_counts* info) {
+  if (!network || !info) return fail(DDR_ERR_ARG, "network_info: null argument");
+  const auto* nw = static_cast<const Network*>(network);
+  info->n = nw->n;
+  info->kept = nw->kept;
+  info->nnz = nw->nnz;
+  info->n_dropped = nw->n_dropped;
+  info->n_basins = nw->n_basins;
+  info->max_depth = nw->max_depth;
+  info->device = nw->device;
+  return DDR_OK;
+}
+ddr_status ddr_network_get(ddr_network network, int32_t* position, int64_t* order, int32_t* down, int32_t* rows,
+                           int32_t* cols, int32_t* dropped, void* stream) {
+  DDR_GUARD({
+    return network_get(static_cast<const Network*>(network), position, order, down, rows, cols, dropped,
+                       static_cast<hipStream_t>(stream));
+  })
+}
+ddr_status ddr_network_destroy(ddr_network network) {
+  network_destroy(static_cast<Network*>(network));
+  return DDR_OK;
+}
+ddr_status ddr_network_lookup_i64(int64_t n, const int64_t* ids, int64_t m, const int64_t* queries, int32_t* pos,
+                                  int32_t flags, void* stream) {
+  DDR_GUARD({ return network_lookup(n, ids, m, queries, pos, flags, static_cast<hipStream_t>(stream)); })
+}
+ddr_status ddr_network_lookup_i64_host(int64_t n, const int64_t* ids, int64_t m, const int64_t* queries,
+                                       int32_t* pos) {
+  DDR_GUARD({ return network_lookup_host(n, ids, m, queries, pos); })
 }
 ddr_status ddr_attr_prepare_f32(int64_t n_rows, int32_t n_features, const float* raw, int64_t feat_stride,
                                 const double* scale, const double* offset, const int32_t* log10_flag,

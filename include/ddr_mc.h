@@ -789,6 +789,47 @@ ddr_status ddr_upstream_member_counts_host(ddr_upstream_index index, int64_t n_g
 ddr_status ddr_upstream_members_host(ddr_upstream_index index, int64_t n_gauges, const int32_t* gage_idx,
                                      const int64_t* off, int32_t* idx);
 
+/* The network build: a raw flowpath table in any row order to the contract every other entry point starts from
+ * (strictly lower-triangular COO, upstream reaches numbered first, dendritic).  It replaces the engine's
+ * create_matrix (engine/src/ddr_engine/merit/build.py:20-107, lynker_hydrofabric/io.py:60-154: rustworkx topological
+ * sort, cycle removal, renumbering).  ids[n] are distinct int64 over the full range, to_ids[n] the id of each row's
+ * downstream flowpath.  One deterministic answer, identical bits from the device build and its host twin:
+ *   1. down[i] = the row of to_ids[i] in ids, -1 when no row has that id: an outlet (0, negative, any foreign id).
+ *   2. A reach is on a cycle if following down returns to it (a self-loop counts).  On-cycle reaches are dropped, a
+ *      kept reach that drained into one becomes an outlet, reaches upstream of a cycle are kept.
+ *   3. dist = edges to the outlet, basin = the rank of the outlet's row among all outlets' rows.  The new index sorts
+ *      the kept reaches by (basin ascending, dist descending, row ascending): basins are contiguous, row > col.
+ *
+ * ddr_network_build: on the current device and `stream`; ids / to_ids are host arrays, or with
+ *   DDR_NETWORK_DEVICE_INPUT device arrays.  Synchronous (the counts come back).  ddr_network_build_host: the same
+ *   without a device.  n == 0 gives an empty network.
+ * ddr_network_info: kept = n - n_dropped reaches, nnz edges, n_basins outlets, max_depth the longest reach-to-outlet
+ *   path in edges; device = -1 for a host build.
+ * ddr_network_get: copies out position (int32[kept]: the row of new reach k), order (int64[kept]: its id), down
+ *   (int32[kept]: new index of its downstream reach, -1), rows / cols (int32[nnz], the COO in ascending cols),
+ *   dropped (int32[n_dropped], rows ascending).  NULL skips an array.  Host pointers; a device build also takes
+ *   device pointers, and copies on `stream` before it returns.
+ * ddr_network_lookup_i64 / _host: pos[k] (int32[m]) = the row of queries[k] in ids, -1 when absent; with
+ *   DDR_NETWORK_DEVICE_INPUT every array of the device form is device memory.  Synchronous.
+ *
+ * Refused with DDR_ERR_ARG and a message naming the fault: null pointers, negative counts, an unknown flag, n >= 2^30
+ * (all before any launch), and an id that appears more than once in ids (the message names the smallest one). */
+typedef void* ddr_network;
+enum { DDR_NETWORK_DEVICE_INPUT = 1 };
+typedef struct {
+  int64_t n, kept, nnz, n_dropped, n_basins, max_depth, device;
+} ddr_network_counts;
+ddr_status ddr_network_build(int64_t n, const int64_t* ids, const int64_t* to_ids, int32_t flags, void* stream,
+                             ddr_network* network);
+ddr_status ddr_network_build_host(int64_t n, const int64_t* ids, const int64_t* to_ids, ddr_network* network);
+ddr_status ddr_network_info(ddr_network network, ddr_network_counts* info);
+ddr_status ddr_network_get(ddr_network network, int32_t* position, int64_t* order, int32_t* down, int32_t* rows,
+                           int32_t* cols, int32_t* dropped, void* stream);
+ddr_status ddr_network_destroy(ddr_network network);
+ddr_status ddr_network_lookup_i64(int64_t n, const int64_t* ids, int64_t m, const int64_t* queries, int32_t* pos,
+                                  int32_t flags, void* stream);
+ddr_status ddr_network_lookup_i64_host(int64_t n, const int64_t* ids, int64_t m, const int64_t* queries, int32_t* pos);
+
 /* The geometry predictor around the KAN (src/ddr/geometry/predictor.py, adapters.py): two launches that with
  * ddr_kan_forward_f32 between them take raw catchment attributes to channel geometry.  Device pointers, fp32
  * unless stated, no host sync, no allocation; n_rows == 0 is a no-op.
