@@ -853,6 +853,18 @@ const void* backward_kernel_of(const Graph* g, bool gs, bool df = false, int pl 
   }
   return gs ? (const void*)route_backward_kernel<R, KR, true> : (const void*)route_backward_kernel<R, KR, false>;
 }
+// Whether a launch runs the exact adjoint of the fp32 trajectory (DF): on request (DDR_BWD_EXACT_ADJOINT), and
+// for every hot-started window of at most kExactShortT steps.  A hot start is the steady state of q'[0], so
+// the first steps' mass imbalances are only what q' has drifted since: the parameter gradient is the remainder
+// of terms that cancel to 1e-2 ... 1e-3 of their size, and the default adjoint's Q - x~ from the stored fp32 x(t)
+// (physics.h) is 1.3e-4 / 5.2e-5 / 2.5e-5 / 1.4e-5 of the gradient at T = 3 / 4 / 5 / 6 on a 300-reach tree
+// (tests/test_gpu_time_axis.py), above the 5e-5 the fp32 gradients hold elsewhere.  DF holds 5e-7 there, and its
+// extra work on a launch of a few ticks is not measurable.  Carried windows (route_timestep chains) start from
+// an arbitrary state and keep the default.
+constexpr int64_t kExactShortT = 8;
+inline bool backward_exact_of(const RouteArgs& a) {
+  return (a.flags & DDR_BWD_EXACT_ADJOINT) != 0 || (!(a.flags & DDR_FWD_CARRY) && a.T <= kExactShortT);
+}
 // the plain backward instance a launch can take (route_backward_kernel's PL), 0 when none
 inline int backward_plain_of(const Graph* g, const RouteArgs& a) {
   if ((a.flags & kFlagNoPlain) || g->split.nranks > 0 || a.prof != nullptr || a.gseed != nullptr || (a.T & 3) != 0) return 0;
@@ -866,8 +878,7 @@ hipError_t launch_backward_kr(const Graph* g, RouteArgs a, hipStream_t stream) {
   const RouteLds lds = route_lds_plan<R>(g, true, bwd_xb_of<R>(g));
   set_launch_args(a, g, lds);
   const dim3 grid((unsigned)g->blocks.size()), block(kBlockThreads);
-  const void* kern = backward_kernel_of<R, KR>(g, a.gqs != nullptr, (a.flags & DDR_BWD_EXACT_ADJOINT) != 0,
-                                                backward_plain_of(g, a));
+  const void* kern = backward_kernel_of<R, KR>(g, a.gqs != nullptr, backward_exact_of(a), backward_plain_of(g, a));
   hipError_t e = hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds.smem);
   if (e != hipSuccess) return e;
   void* kargs[] = {&a};

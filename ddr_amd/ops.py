@@ -472,7 +472,9 @@ def route(graph: RiverGraph, qprime: torch.Tensor, n: torch.Tensor, q: torch.Ten
     computed (~1e-7 norm-relative on any depth; the fp32 default is ~1e-3 on a 2215-deep basin, ~1e-7 on
     shallow ones) at ~30 % more backward time (q' re-read, fp64 upstream sums: DDR_BWD_EXACT_ADJOINT).  The
     fp64 model's own gradient differs from both by the fp32 states' rounding (~1e-3 there); route in fp64 for
-    that."""
+    that.  A hot-started window of at most 8 steps always runs it: that close to the hot start's steady state the
+    gradient is the remainder of nearly cancelled terms, which the default adjoint holds to 1e-4 only
+    (``backward_exact_of``, route_backward.h)."""
     dt = qprime.dtype
     dev = qprime.device
 

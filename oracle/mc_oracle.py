@@ -469,13 +469,13 @@ def geometry_statistics(n, p, q, slope, daily_q: np.ndarray, bd: Bounds = Bounds
 # ---------------------------------------------------------------------------------------------
 
 
-def _celerity_vjp(Q, n, q, p, slope, bd: Bounds, g_c):
-    """VJP of c = trapezoid_celerity(Q, n, q, p, S) -> (gQ, gn, gq, gp); fp64.
+def _celerity_vjp(Q, n, q, p, slope, bd: Bounds, g_c, dtype=np.float64):
+    """VJP of c = trapezoid_celerity(Q, n, q, p, S) -> (gQ, gn, gq, gp); fp64 (``dtype``: see ``route_backward``).
 
     Clamp gradients are inclusive at the bounds (torch.clamp backward passes grad where
     lo <= x <= hi), matching the reference's autograd.
     """
-    d = trapezoid_celerity(Q, n, q, p, slope, bd, np.float64, full=True)
+    d = trapezoid_celerity(Q, n, q, p, slope, bd, dtype, full=True)
     sS = np.sqrt(slope)
     g_vc = g_c * 5.0 / 3.0
     g_v = g_vc * ((d["v"] >= bd.velocity) & (d["v"] <= bd.velocity_max))
@@ -566,7 +566,7 @@ def geometry_vjp(Q, n, q, p, slope, bd: Bounds, g_tw, g_ss):
 
 def route_backward(net: Network, r: Reaches, qprime: np.ndarray, xs: np.ndarray, grad_runoff: np.ndarray,
                    bd: Bounds = Bounds(), dt=3600.0, outflow_idx=None, want_qprime=False, carry=False,
-                   state_seed=None):
+                   state_seed=None, dtype=np.float64):
     """Adjoint of ``route`` w.r.t. (n, q_spatial, p_spatial) (and optionally q' and the state), fp64.
 
     ``xs`` is the (T, N) unclamped solve output of the forward (``xs[0]`` = Q0).
@@ -577,8 +577,11 @@ def route_backward(net: Network, r: Reaches, qprime: np.ndarray, xs: np.ndarray,
     (mmc.py:330-342, 487-559); ``q0`` of the result is then dL/dQ0.
     ``state_seed`` (2, N): per-reach dL/dQ_{T-1} (the final ``_discharge_t``, mmc.py:441) and dL/dQ_{T-2} (the
     state of the reported geometry, mmc.py:161-162; ``geometry_vjp``), added to those steps' dL/dQ.
+    ``dtype`` = float32: the same sweep with every element-wise operation and every running sum in fp32 and the
+    transposed solves in fp64 rounded to fp32 -- the precision of the reference's fp32 autograd (its solves
+    run on fp64 copies, utils.py:188-242), as a measure of what an fp32 adjoint can hold; not a checker.
     """
-    f = np.float64
+    f = dtype
     r = r.astype(f)
     xs = np.asarray(xs, dtype=f)
     qprime = np.asarray(qprime, dtype=f)
@@ -589,7 +592,7 @@ def route_backward(net: Network, r: Reaches, qprime: np.ndarray, xs: np.ndarray,
     Qall = np.maximum(xs, qlb)
     Q0 = xs[0] if carry else Qall[0]  # the state step 1 reads
     if gauge:
-        g_all = np.zeros((T, N))
+        g_all = np.zeros((T, N), dtype=f)
         for g, idx in enumerate(outflow_idx):
             idx = np.asarray(idx, dtype=np.int64) % N
             # output[:, 0] = clamp(sum of the gauge's initial states) (mmc.py:398-412)
@@ -604,11 +607,11 @@ def route_backward(net: Network, r: Reaches, qprime: np.ndarray, xs: np.ndarray,
         g_all[T - 1] += sd[0]
         if T >= 2:
             g_all[T - 2] += sd[1]
-    lam = np.zeros(N)
-    gn = np.zeros(N)
-    gq = np.zeros(N)
-    gp = np.zeros(N)
-    gqp = np.zeros((T, N)) if want_qprime else None
+    lam = np.zeros(N, dtype=f)
+    gn = np.zeros(N, dtype=f)
+    gq = np.zeros(N, dtype=f)
+    gp = np.zeros(N, dtype=f)
+    gqp = np.zeros((T, N), dtype=f) if want_qprime else None
     p_full = np.broadcast_to(r.p, (N,)).astype(f)
     for t in range(T - 1, 0, -1):
         lam = lam + g_all[t]
@@ -618,8 +621,8 @@ def route_backward(net: Network, r: Reaches, qprime: np.ndarray, xs: np.ndarray,
             Qp = Q0
         c, _, _ = trapezoid_celerity(Qp, r.n, r.q, p_full, r.slope, bd, f)
         c1, c2, c3, c4 = muskingum_coefficients(r.length, c, r.x, dt, f)
-        gb = net.upper_solve(c1, gx)
-        qc = np.maximum(qprime[t - 1], qlb)
+        gb = net.upper_solve(c1, gx).astype(f)
+        qc = np.maximum(qprime[t - 1], f(qlb))
         Sx = net.spmv(xs[t])
         I = net.spmv(Qp)
         gc1 = gb * Sx
@@ -634,11 +637,11 @@ def route_backward(net: Network, r: Reaches, qprime: np.ndarray, xs: np.ndarray,
                   + gc3 * (1.0 - X) * (1.0 - c3) - gc4 * c4 * (1.0 - X)) / den
         g_k = 2.0 * g_twok
         g_c = -g_k * (r.length / c) / c
-        gQc, gn_t, gq_t, gp_t = _celerity_vjp(Qp, r.n, r.q, p_full, r.slope, bd, g_c)
+        gQc, gn_t, gq_t, gp_t = _celerity_vjp(Qp, r.n, r.q, p_full, r.slope, bd, g_c, f)
         gn += gn_t
         gq += gq_t
         gp += gp_t
-        up_push = np.zeros(N)
+        up_push = np.zeros(N, dtype=f)
         has_down = net.down >= 0
         dn = net.down[has_down]
         up_push[has_down] = gb[dn] * c2[dn]
@@ -653,7 +656,7 @@ def route_backward(net: Network, r: Reaches, qprime: np.ndarray, xs: np.ndarray,
     if want_qprime and not carry:
         # hot start: Q0 = clamp(solve(I - N, q'[0]))
         gx0 = lam * (xs[0] >= qlb)
-        gqp[0] += net.upper_solve(np.ones(N), gx0)
+        gqp[0] += net.upper_solve(np.ones(N), gx0).astype(f)
     p_is_scalar = np.ndim(r.p) == 0
     return dict(n=gn, q_spatial=gq, p_spatial=(gp.sum() if p_is_scalar else gp), qprime=gqp, lam0=lam, q0=g0)
 
