@@ -44,6 +44,8 @@ DDR_FWD_FAST_MATH = 16
 DDR_FWD_FAITHFUL_MATH = 32
 DDR_FWD_CHECK_QPRIME = 64
 DDR_BWD_EXACT_ADJOINT = 128
+DDR_LIN_END = 1     # ddr_lin_route_*: the state after each interval's last sub-step (default: the interval mean)
+DDR_LIN_STEADY = 2  # ddr_lin_route_*: start from the steady state of forcing row 0
 DDR_PERIOD_DIRECT_STORE = 1 << 24  # ddr_period_daily_*: the per-thread store variant (A/B timing)
 
 DDR_DEBUG_FORCE_TIMEOUT = 1
@@ -237,6 +239,11 @@ _SIGS = {
     "ddr_period_daily_f64": (C.c_int, [_P, _P, _I64, C.POINTER(Gauges), C.c_double, _I32, _I64, _I64, _I64, _P, _P]),
     "ddr_geometry_stats_f32": (C.c_int, [_P, _I64, _I64, _I64, _I64, _P, _P, _I64, _P, _P, C.c_double, C.c_double,
                                          _P, _P]),
+    "ddr_lin_work_bytes": (_I64, [_P, _I64, _I32]),
+    "ddr_lin_route_f32": (C.c_int, [_P, _P, _P, C.c_double, _I64, _I64, _P, _P, _P, _P, _I32, _P, _P, _P, _P, _P, _P]),
+    "ddr_lin_route_f64": (C.c_int, [_P, _P, _P, C.c_double, _I64, _I64, _P, _P, _P, _P, _I32, _P, _P, _P, _P, _P, _P]),
+    "ddr_lin_gauge_f32": (C.c_int, [_I64, _I64, C.POINTER(Gauges), _P, _P, _P]),
+    "ddr_lin_gauge_f64": (C.c_int, [_I64, _I64, C.POINTER(Gauges), _P, _P, _P]),
     "ddr_graph_status": (C.c_int, [_P, _P]),
     "ddr_xmem_alloc": (C.c_int, [_I64, C.POINTER(C.c_void_p), _P, C.POINTER(C.c_int32)]),
     "ddr_xmem_open": (C.c_int, [_P, C.POINTER(C.c_void_p)]),

@@ -11,6 +11,7 @@
 
 #include "internal.h"
 #include "route_args.h"
+#include "route_linear.h"
 #include "metrics.h"
 #include "objective.h"
 #include "train.h"
@@ -802,6 +803,80 @@ ddr_status state_impl(const ddr_graph* gh, const R* x_save, int64_t T, int64_t t
   hipStream_t s = static_cast<hipStream_t>(stream);
   DDR_TRY(ready_for(g, s));
   DDR_HIP(launch_state_at<R>(g, T, t, qlb, (flags & DDR_FWD_CARRY) != 0, x_save, out, s));
+  return DDR_OK;
+}
+
+// Linear Muskingum routing (route_linear.hip): the forcing gathered once into the schedule's row layout
+// (one row per forcing interval), the status block and the granules re-initialised as for the forward.
+template <typename R>
+ddr_status lin_route_impl(const ddr_graph* gh, const R* k, const R* x, double dt, int64_t S, int64_t F, const R* qext,
+                          const R* fs, const uint8_t* valid, const R* q0, int32_t flags, R* out, R* q_last, void* work,
+                          double* bnd, void* status, void* stream) {
+  if (!gh || !k || !x || !qext || !out || !q_last) return fail(DDR_ERR_ARG, "null linear-routing argument");
+  const Graph* g = reinterpret_cast<const Graph*>(gh);
+  if (!g->uploaded) return fail(DDR_ERR_ARG, "graph was built host-only: upload it first (ddr_graph_upload)");
+  if (g->split.nranks > 0) return fail(DDR_ERR_ARG, "split basin: linear routing is not supported");
+  if (S < 1 || F < 1) return fail(DDR_ERR_ARG, "substeps and forcing intervals must be >= 1");
+  if (flags & ~(DDR_LIN_END | DDR_LIN_STEADY)) return fail(DDR_ERR_ARG, "unknown linear-routing flag");
+  if ((flags & DDR_LIN_STEADY) && q0) return fail(DDR_ERR_ARG, "DDR_LIN_STEADY takes no q0");
+  // ticks of the deepest block (F * S + 1 states + its depth) in an int; the forcing rows too
+  if (F > INT32_MAX || S > INT32_MAX || F > (INT32_MAX - 2 - g->max_block_depth) / S)
+    return fail(DDR_ERR_ARG, "F * S + the deepest block exceeds the tick counter");
+  if (F * (g->n + 1) > (int64_t(1) << 60)) return fail(DDR_ERR_ARG, "F * N overflows");
+  if (!work) return fail(DDR_ERR_ARG, "null workspace (ddr_lin_work_bytes)");
+  if (g->n_cut > 0 && !bnd) return fail(DDR_ERR_ARG, "graph has cut edges: bnd buffer required");
+  if (!status) return fail(DDR_ERR_ARG, "null status block");
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const bool cap = capturing(s);
+  ddr_status st;
+  if (!cap && (st = g_pending.check(false))) return st;
+  const int res = linear_resident_blocks<R>(g);
+  if (res < 0) return fail(DDR_ERR_HIP, "occupancy query failed");
+  if (res == 0)
+    return fail(DDR_ERR_CAPACITY, "the linear routing kernel does not fit a CU at this schedule's LDS size");
+  DDR_TRY(ready_for(g, s));
+  const int64_t TS = F * S + 1;
+  DDR_HIP(hipMemsetAsync(status, 0, kStatusBytes, s));
+  if (g->n_cut > 0) DDR_HIP(hipMemsetAsync(bnd, 0xFF, sizeof(double) * g->n_cut * TS, s));
+  RouteArgs ga;  // the gather's view: qext rows as a q' store in the row layout, one row per interval
+  std::memset(&ga, 0, sizeof(ga));
+  ga.s = g->dev;
+  ga.N = g->n;
+  ga.T = TS;
+  ga.qp_hours = (int32_t)S;
+  ga.qp_shift = 0;
+  ga.qs_rows = (int32_t)F;
+  ga.qprime = qext;
+  ga.fs = fs;
+  ga.qp_valid = valid;
+  ga.qs = work;
+  DDR_HIP(launch_gather_qprime<R>(g, ga, s));
+  LinArgs a;
+  std::memset(&a, 0, sizeof(a));
+  a.s = g->dev;
+  a.N = g->n;
+  a.F = F;
+  a.S = (int32_t)S;
+  a.TS = (int32_t)TS;
+  a.flags = flags | (g_debug & kFlagForceTimeout);
+  a.dt = dt;
+  a.k = k;
+  a.x = x;
+  a.q0 = q0;
+  a.qs = work;
+  a.out = out;
+  a.q_last = q_last;
+  a.bnd = bnd;
+  a.status = static_cast<unsigned*>(status);
+  DDR_HIP(launch_route_linear<R>(g, a, s));
+  return cap ? DDR_OK : g_pending.enqueue(status, s, "linear", gh);
+}
+
+template <typename R>
+ddr_status lin_gauge_impl(int64_t N, int64_t F, const ddr_gauges* gz, const R* nf, R* out, void* stream) {
+  if (!gz || !nf || !out || N < 1 || F < 1) return fail(DDR_ERR_ARG, "bad linear gauge arguments");
+  if (gz->n_gauges > 0 && (!gz->offsets || !gz->index)) return fail(DDR_ERR_ARG, "null gauge arrays");
+  DDR_HIP(launch_linear_gauge<R>(gz->n_gauges, F, gz->offsets, gz->index, nf, out, static_cast<hipStream_t>(stream)));
   return DDR_OK;
 }
 
@@ -1699,6 +1774,30 @@ ddr_status ddr_geometry_stats_f32(const float* q_daily, int64_t reach_stride, in
                                   static_cast<hipStream_t>(stream)));
     return DDR_OK;
   })
+}
+
+int64_t ddr_lin_work_bytes(const ddr_graph* g, int64_t F, int32_t real_bytes) {
+  if (!g || F < 1 || (real_bytes != 4 && real_bytes != 8)) return -1;
+  return (int64_t)align16((size_t)real_bytes * (size_t)(reinterpret_cast<const Graph*>(g)->n * F));
+}
+ddr_status ddr_lin_route_f32(const ddr_graph* g, const float* k, const float* x, double dt, int64_t S, int64_t F,
+                             const float* qext, const float* flow_scale, const uint8_t* valid, const float* q0,
+                             int32_t flags, float* out, float* q_last, void* workspace, double* bnd, void* status,
+                             void* stream) {
+  DDR_GUARD({ return lin_route_impl<float>(g, k, x, dt, S, F, qext, flow_scale, valid, q0, flags, out, q_last, workspace, bnd, status, stream); })
+}
+ddr_status ddr_lin_route_f64(const ddr_graph* g, const double* k, const double* x, double dt, int64_t S, int64_t F,
+                             const double* qext, const double* flow_scale, const uint8_t* valid, const double* q0,
+                             int32_t flags, double* out, double* q_last, void* workspace, double* bnd, void* status,
+                             void* stream) {
+  DDR_GUARD({ return lin_route_impl<double>(g, k, x, dt, S, F, qext, flow_scale, valid, q0, flags, out, q_last, workspace, bnd, status, stream); })
+}
+ddr_status ddr_lin_gauge_f32(int64_t N, int64_t F, const ddr_gauges* gauges, const float* nf, float* out, void* stream) {
+  DDR_GUARD({ return lin_gauge_impl<float>(N, F, gauges, nf, out, stream); })
+}
+ddr_status ddr_lin_gauge_f64(int64_t N, int64_t F, const ddr_gauges* gauges, const double* nf, double* out,
+                             void* stream) {
+  DDR_GUARD({ return lin_gauge_impl<double>(N, F, gauges, nf, out, stream); })
 }
 
 ddr_status ddr_graph_status(const void* status, void* stream) {

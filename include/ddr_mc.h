@@ -26,6 +26,8 @@
  *   ddr_gauge_reduce    mmc.py:344-363, 405-411, 433-439 (ragged outflow_idx scatter_add)
  *   ddr_tri_solve       routing/utils.py:695 triangular_sparse_solve (general CSR, non-unit diagonal)
  *   ddr_tri_grad_values routing/utils.py:321-389 _compute_A_gradients (gradA = -gradb[row]*x[col])
+ *   ddr_lin_route       benchmarks/src/ddr_benchmarks/benchmark.py:121-234 (the fixed-parameter linear arm,
+ *                       DiffRoute's LTIRouter with irf_fn="muskingum"), as RAPID's Muskingum scheme
  */
 #ifndef DDR_MC_H
 #define DDR_MC_H
@@ -479,6 +481,38 @@ ddr_status ddr_gauge_reduce_f32(const ddr_graph* g, const float* x_save, int64_t
 ddr_status ddr_gauge_reduce_f64(const ddr_graph* g, const double* x_save, int64_t T,
                                 const ddr_gauges* gauges, double discharge_lb, int32_t flags,
                                 double* runoff, void* stream);
+
+/* Linear Muskingum routing, RAPID's matrix scheme (the fixed-parameter baseline of the reference's
+ * benchmarks/ package): per reach C1 = (h - k x) / den, C2 = (h + k x) / den, C3 = (k (1 - x) - h) / den with
+ * h = dt / 2, den = k (1 - x) + h, and per sub-step
+ *   Q+ = (C1 (In+ + qe) + C2 (In + qe)) + C3 Q,  In+ = sum of the upstream Q+ (upstream-list order)
+ * in the routed precision, separately rounded, no clamps.  One persistent launch routes F * S sub-steps.
+ *   k, x        (N) storage constant (seconds) and weighting factor; dt: the sub-step in seconds
+ *   S, F        sub-steps per forcing interval, forcing intervals; qext (F, N)
+ *   flow_scale  (N) or NULL; valid (N) uint8 or NULL (0: forcing 0.001), as the Muskingum-Cunge forward's
+ *   q0          (N) initial state or NULL (zeros); DDR_LIN_STEADY (q0 NULL): the steady state of qext row 0,
+ *               (I - N)^-1 qext[0] in fp64 (the hot start's sweep)
+ *   out         (N, F): the mean of the S states at the beginning of each sub-step (fp64 sum, one rounding;
+ *               RAPID's Qout), or with DDR_LIN_END the state after the interval's last sub-step
+ *   q_last      (N) the final state (RAPID's Qfinal)
+ *   workspace   ddr_lin_work_bytes bytes; bnd: n_cut * (F * S + 1) doubles (NULL without cut edges);
+ *   status      device status block (status_bytes)
+ * No host synchronisation; capturable.  A split-basin graph is refused. */
+enum { DDR_LIN_END = 1, DDR_LIN_STEADY = 2 };
+int64_t ddr_lin_work_bytes(const ddr_graph* g, int64_t F, int32_t real_bytes);
+ddr_status ddr_lin_route_f32(const ddr_graph* g, const float* k, const float* x, double dt, int64_t S, int64_t F,
+                             const float* qext, const float* flow_scale, const uint8_t* valid, const float* q0,
+                             int32_t flags, float* out, float* q_last, void* workspace, double* bnd, void* status,
+                             void* stream);
+ddr_status ddr_lin_route_f64(const ddr_graph* g, const double* k, const double* x, double dt, int64_t S, int64_t F,
+                             const double* qext, const double* flow_scale, const uint8_t* valid, const double* q0,
+                             int32_t flags, double* out, double* q_last, void* workspace, double* bnd, void* status,
+                             void* stream);
+/* Gauge rows of an (N, F) output of ddr_lin_route: out (G, F), each gauge's reaches added in list order.
+ * (ddr_gauge_reduce reads the Muskingum-Cunge forward's saved states and clamps them; this output has neither.) */
+ddr_status ddr_lin_gauge_f32(int64_t N, int64_t F, const ddr_gauges* gauges, const float* nf, float* out, void* stream);
+ddr_status ddr_lin_gauge_f64(int64_t N, int64_t F, const ddr_gauges* gauges, const double* nf, double* out,
+                             void* stream);
 
 /* Gauge-mode training objective, fused (scripts/train.py:78-82 + io/functions.py:7-23): daily area
  * means of the gauge sums over the trimmed window [t0, t0 + L) of the routed states x_save,
