@@ -1,5 +1,6 @@
 // Internal definitions shared by the host graph builder (graph.cpp), the routing kernels
-// (route_forward.hip, route_backward.h) and the C ABI (capi.cpp).  Not part of the public interface (include/ddr_mc.h).
+// (route_forward.hip, route_linear.hip, route_backward.h) and the C ABI (capi.cpp).  Not part of the public interface
+// (include/ddr_mc.h).
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -52,7 +53,7 @@ constexpr int kChunk = 8;
 // Parameter-gradient partial sums are flushed to the fp64 accumulators every kGradFlush steps
 // (aligned to the step index, so the summation grouping does not depend on the partition).
 constexpr int kGradFlush = 128;
-__host__ __device__ inline size_t align16(size_t x) { return (x + 15) / 16 * 16; }
+__host__ __device__ constexpr size_t align16(size_t x) { return (x + 15) / 16 * 16; }
 // LDS slots per buffer of the routing kernels: every block's nloc + nvirt slots, one zero slot
 // (missing upstreams of the forward read it), rounded up to even (16-B aligned statics rows).
 __host__ __device__ inline int route_slot_stride(int max_slots) { return (max_slots + 2) & ~1; }
@@ -69,15 +70,59 @@ inline int kr_of_load(int64_t max_load) {
   while (int64_t(kr) * kBlockThreads < max_load) kr *= 2;
   return kr;
 }
-// Dynamic LDS of the routing kernels (route_forward.hip, route_backward.h), for `slots` = nloc + nvirt slots and `nring`
-// import rings (virtual inflows forward, cut-outs backward), reals of `rsize` bytes:
-//   forward : x slots (f64, xbuf buffers) | 6 statics (R) | ring [nvirt][kChunkFwd] f64
-//   backward: A slots (R) | B slots (R) | published x slots (R) (each xbuf buffers) | 6 statics (R)
-//             | ring [ncout][kChunkBwd][2] (R)
-//             | owner words
-// and then the block's confluence lists (after the math tables of fastmath.h, which occupy the first
-// kMathTabBytes)
+// Dynamic LDS of the routing kernels (route_forward.hip, route_linear.hip, route_backward.h) for `S` slots per
+// buffer (route_slot_stride) and `xbuf` slot buffers.  The math tables of fastmath.h occupy the first
+// kMathTabBytes; then the slot arrays and the statics (fwd_lds / bwd_lds: the kernels' pointers; their bytes,
+// 16-B aligned: fwd_slots_bytes / bwd_slots_bytes), the import ring, the backward's owner words
+// (route_own_bytes) and the block's confluence lists, which close the layout (route_lds_bytes).
 constexpr size_t kMathTabBytes = 3072;
+// Per-reach statics row (StatTab: n, qe, p, sqrtS, L, X).  The linear kernel keeps its [S][kLinCoefs]
+// coefficient table (C1, C2, C3, 0) in the same region.
+constexpr int kStatWords = 6;
+constexpr int kLinCoefs = 4;
+static_assert(kLinCoefs <= kStatWords, "the linear coefficients live in the statics region");
+// forward: x [xbuf][S] f64 | stat [S][kStatWords] R | ring [nvirt][kChunkFwd] f64
+template <typename R>
+struct FwdLds {
+  double* x;
+  R* stat;
+  double* ring;
+};
+__host__ __device__ constexpr size_t fwd_slots_bytes(size_t S, int xbuf, size_t rsize) {
+  return align16(S * (8 * xbuf + kStatWords * rsize));
+}
+template <typename R>
+__device__ __forceinline__ FwdLds<R> fwd_lds(unsigned char* smem, int S, int xbuf) {
+  FwdLds<R> l;
+  l.x = reinterpret_cast<double*>(smem + kMathTabBytes);
+  l.stat = reinterpret_cast<R*>(l.x + xbuf * S);
+  l.ring = reinterpret_cast<double*>(smem + kMathTabBytes + fwd_slots_bytes(S, xbuf, sizeof(R)));
+  return l;
+}
+// backward: a (c1 gb) | b (c2 gb) | x (published x), each [xbuf][S] R | stat [S][kStatWords] R
+//           | ring [ncout][kChunkBwd][2] R
+template <typename R>
+struct BwdLds {
+  R *a, *b, *x, *stat, *ring;
+};
+__host__ __device__ constexpr size_t bwd_slots_bytes(size_t S, int xbuf, size_t rsize) {
+  return align16(S * (3 * xbuf + kStatWords) * rsize);
+}
+template <typename R>
+__device__ __forceinline__ BwdLds<R> bwd_lds(unsigned char* smem, int S, int xbuf) {
+  BwdLds<R> l;
+  l.a = reinterpret_cast<R*>(smem + kMathTabBytes);
+  l.b = l.a + xbuf * S;
+  l.x = l.b + xbuf * S;
+  l.stat = l.x + xbuf * S;
+  l.ring = reinterpret_cast<R*>(smem + kMathTabBytes + bwd_slots_bytes(S, xbuf, sizeof(R)));
+  return l;
+}
+// backward: per hand-off owner thread (tid < max(nvirt, ncout)) its virtual's downstream slot and its
+// cut-out's tick offset, one word
+__host__ __device__ inline size_t route_own_bytes(size_t nvirt, size_t ncout, bool backward) {
+  return backward ? align16(4 * (nvirt > ncout ? nvirt : ncout)) : 0;
+}
 // Confluence lists (reaches with more than two inflows) of a block, in LDS after the ring: at most
 // kMaxConfluenceList int32 entries per block (13-bit offsets in the packed upstream word).
 constexpr int kMaxConfluenceList = 8191;
@@ -85,13 +130,10 @@ __host__ __device__ inline size_t route_lds_bytes(size_t slots, size_t nvirt, si
                                                   size_t rsize, int kr = 4, int xb = 0) {
   // xb: the slot buffers when not the KR rule's (the forward's double-buffered KR = 4 variant; the
   // backward's single-buffered fp64 KR = 2 variant, whose double buffer does not fit)
-  const size_t base = backward ? slots * (3 * (size_t)(xb > 0 ? xb : bwd_xbuf(kr)) + 6) * rsize
-                               : slots * (8 * (size_t)(xb > 0 ? xb : fwd_xbuf(kr)) + 6 * rsize);
+  const size_t base = backward ? bwd_slots_bytes(slots, xb > 0 ? xb : bwd_xbuf(kr), rsize)
+                               : fwd_slots_bytes(slots, xb > 0 ? xb : fwd_xbuf(kr), rsize);
   const size_t ring = backward ? ncout * kChunkBwd * 2 * rsize : nvirt * kChunkFwd * 8;
-  // backward: per hand-off owner thread (tid < max(nvirt, ncout)) its virtual's downstream slot and
-  // its cut-out's tick offset
-  const size_t own = backward ? align16(4 * (nvirt > ncout ? nvirt : ncout)) : 0;
-  return kMathTabBytes + align16(base) + align16(ring) + own + nxl * 4;
+  return kMathTabBytes + base + align16(ring) + route_own_bytes(nvirt, ncout, backward) + nxl * 4;
 }
 
 // One workgroup's slice of the schedule.  Reaches of a block occupy internal positions

@@ -77,12 +77,13 @@ __global__ void __launch_bounds__(kBlockThreads, kBlocksPerCU * kBlockThreads / 
   // [S] each, a publish phase and a compute phase between two barriers.
   constexpr int kXB = XB > 0 ? XB : bwd_xbuf(KR);
   constexpr bool kDbl = kXB == 2 && KR <= kBwdEarlyMaxKR;
-  R* sa = reinterpret_cast<R*>(smem + kMathTabBytes);  // [kXB][S] c1_i gb_i (transposed solve, rounded to R)
-  R* sb = sa + kXB * S;                                 // [kXB][S] c2_i gb_i (adjoint of the inflow)
-  R* sx = sb + kXB * S;                                 // [kXB][S] x(t - 2) of each reach / virtual inflow; [S-1] = 0
-  const StatTab<R> tab{sx + kXB * S};                   // [S][6]
-  R* ring = reinterpret_cast<R*>(smem + kMathTabBytes + align16(size_t(S) * (3 * kXB + 6) * sizeof(R)));  // [ncout][kChunkBwd][2]
-  int* xl = reinterpret_cast<int*>(smem + a.xl_off);                                            // confluence lists
+  const BwdLds<R> lds = bwd_lds<R>(smem, S, kXB);
+  R* sa = lds.a;  // [kXB][S] c1_i gb_i (transposed solve, rounded to R)
+  R* sb = lds.b;  // [kXB][S] c2_i gb_i (adjoint of the inflow)
+  R* sx = lds.x;  // [kXB][S] x(t - 2) of each reach / virtual inflow; [S-1] = 0
+  const StatTab<R> tab{lds.stat};  // [S][6]
+  R* ring = lds.ring;              // [ncout][kChunkBwd][2]
+  int* xl = reinterpret_cast<int*>(smem + a.xl_off);  // confluence lists
   const Consts<R> cs = consts_of<R>(a, true, KR >= kOpqInfMinKR);
   const int64_t T = a.T;
   const bool carry = a.flags & DDR_FWD_CARRY;
@@ -150,7 +151,7 @@ __global__ void __launch_bounds__(kBlockThreads, kBlocksPerCU * kBlockThreads / 
       if (gauge && a.g_roff[ref[k] + 1] - a.g_roff[ref[k]] == 1) gsg[k] = (int)a.g_rg[a.g_roff[ref[k]]];
     }
     od[k] = ((unsigned)a.s.off[P] << 16) | ((unsigned)a.s.dloc[P] & 0xFFFFu) | (nograd ? 0x80000000u : 0u);
-    up[k] = pack_up(a, P, (unsigned)(S - 1));  // slot S-1 holds 0: missing upstreams add exactly 0
+    up[k] = pack_up(a.s, P, (unsigned)(S - 1));  // slot S-1 holds 0: missing upstreams add exactly 0
     lam[k] = R(0);
     sxn[k] = SxT(0);
     xc[k] = xa[k] = xb[k] = R(0);
@@ -190,7 +191,7 @@ __global__ void __launch_bounds__(kBlockThreads, kBlocksPerCU * kBlockThreads / 
   // global load and wait for none at the tick's top (a cold 16-B group load, one tick ahead, paced the light
   // backward: profiles/r05/ab_r05.txt item 12)
   const bool ghelp = kStatReg && kShiftG && xhelp && !(gauge);
-  R* const sg = reinterpret_cast<R*>(sx + kXB * S);  // [2][S] (ghelp): dL/drunoff of each reach's step, by tick parity
+  R* const sg = lds.stat;  // [2][S] (ghelp): dL/drunoff of each reach's step, by tick parity
   // virtual inflow owners (tid < nvirt): v_edge, v_off in registers; in LDS (own[tid], registers are
   // full) the virtual's consumer slot (low 16 bits) and the tick offset of cut-out `tid` (high 16 bits,
   // tid < ncout: its import owner)
@@ -206,7 +207,7 @@ __global__ void __launch_bounds__(kBlockThreads, kBlocksPerCU * kBlockThreads / 
   auto v_dloc_of = [&]() { return (int)(own[tid] & 0xFFFFu); };
   const int TT = (int)T + B.dmax;
   load_math_tables();
-  load_xlist(a, B, xl);
+  load_xlist(a.s, B, xl);
   // split basin: [nvirt] the virtuals' export rows (to the producer block's rank), then [ncout] the
   // cut-outs' import rows (this rank's receive rows for edges from another rank's consumer)
   uintptr_t* xtv = reinterpret_cast<uintptr_t*>(smem + xt_off);
@@ -395,8 +396,8 @@ __global__ void __launch_bounds__(kBlockThreads, kBlocksPerCU * kBlockThreads / 
           double g[2];
           const uintptr_t p = xt_off ? xtc[c] : reinterpret_cast<uintptr_t>(a.bwd_bnd + (int64_t)(B.cout0 + c) * T * 2);
           const double* row = reinterpret_cast<const double*>(p & ~uintptr_t(1)) + (int64_t)t * 2;
-          if (p & 1u) wait_granules<2, true>(row, 0, 1, 0, 2, g, a.status, bid, force_to);  // another rank's consumer
-          else wait_granules<2>(row, 0, 1, 0, 2, g, a.status, bid, force_to);
+          if (p & 1u) wait_granules<2, true>(row, 0, 0, 2, g, a.status, bid, force_to);  // another rank's consumer
+          else wait_granules<2>(row, 0, 0, 2, g, a.status, bid, force_to);
           A = R(g[0]);
           Bv = R(g[1]);
         }
@@ -719,8 +720,8 @@ __global__ void __launch_bounds__(kBlockThreads, kBlocksPerCU * kBlockThreads / 
               if (sys) poll_granules<2, true>(row, 0, 0, 2, eg, g, a.status, bid, force_to);
               else poll_granules<2, false>(row, 0, 0, 2, eg, g, a.status, bid, force_to);
             } else {
-              if (sys) wait_granules<2, true>(row, 0, 1, 0, 2, g, a.status, bid, force_to);
-              else wait_granules<2>(row, 0, 1, 0, 2, g, a.status, bid, force_to);
+              if (sys) wait_granules<2, true>(row, 0, 0, 2, g, a.status, bid, force_to);
+              else wait_granules<2>(row, 0, 0, 2, g, a.status, bid, force_to);
             }
             A = R(g[0]);
             Bv = R(g[1]);
@@ -894,21 +895,12 @@ hipError_t launch_backward_kr(const Graph* g, RouteArgs a, hipStream_t stream) {
 
 template <typename R>
 hipError_t launch_route_backward(const Graph* g, const RouteArgs& a, hipStream_t stream) {
-  switch (g->kr) {
-    case 1: return launch_backward_kr<R, 1>(g, a, stream);
-    case 2: return launch_backward_kr<R, 2>(g, a, stream);
-    default: return launch_backward_kr<R, 4>(g, a, stream);
-  }
+  return dispatch_kr(g, [&](auto kr) { return launch_backward_kr<R, decltype(kr)::value>(g, a, stream); });
 }
 
 template <typename R>
 int backward_resident_blocks(const Graph* g) {
-  const void* f = nullptr;
-  switch (g->kr) {
-    case 1: f = backward_kernel_of<R, 1>(g, false); break;
-    case 2: f = backward_kernel_of<R, 2>(g, false); break;
-    default: f = backward_kernel_of<R, 4>(g, false);
-  }
+  const void* f = dispatch_kr(g, [&](auto kr) { return backward_kernel_of<R, decltype(kr)::value>(g, false); });
   return resident_blocks(g, f, route_lds_plan<R>(g, true, bwd_xb_of<R>(g)).smem);
 }
 

@@ -1,5 +1,8 @@
-// Device helpers shared by the fused Muskingum-Cunge routing kernels for gfx950 (MI355X): the forward over
-// all T steps (route_forward.hip) and the reverse-time / reverse-topological adjoint (route_backward.h).
+// Device helpers shared by the fused routing kernels for gfx950 (MI355X): the Muskingum-Cunge forward over
+// all T steps (route_forward.hip), its reverse-time / reverse-topological adjoint (route_backward.h) and the
+// linear Muskingum forward (route_linear.hip).  All three walk the schedule described here; the two forwards
+// share its per-reach words (reach_words), and VirtOwner states the virtual-inflow owner for the linear
+// kernel and any later kernel on this schedule (the Muskingum-Cunge forward keeps scalars of its own).
 //
 // One persistent workgroup owns a block of reaches (whole basins, or a connected piece of a large
 // basin) for the whole time window.  Reach i runs step t at tick t + off(i) with
@@ -89,67 +92,20 @@ __device__ __forceinline__ unsigned long long load_granule_sys(const double* p) 
                            __HIP_MEMORY_SCOPE_SYSTEM);
 }
 
-// Spin until the granules of a chunk are published (bounded).  On a timeout (or with the debug flag
-// that forces one) record it in the status block and return NaN: the corruption then shows in the
-// outputs.
 // Granules requested together by one import batch (register budget: 2 VGPRs each).
 constexpr int kImportBatch = 4;
-// Batched form for the chunk imports: the granules row[t0 + s * stride] (s < C; outside [lo, hi):
-// 0) are all requested before the first wait, so a chunk costs one memory round trip, not C; only
-// the still-unpublished ones are polled again.
-template <int C, bool Sys = false>
-__device__ __forceinline__ void wait_granules(const double* row, int64_t t0, int stride, int64_t lo, int64_t hi,
-                                              double (&out)[C], unsigned* status, int bid, bool force_timeout) {
-  auto ld = [](const double* p) { return Sys ? load_granule_sys(p) : load_granule(p); };
-  unsigned long long v[C];
-  unsigned pend = 0;
-#pragma unroll
-  for (int s = 0; s < C; ++s) {
-    const int64_t t = t0 + (int64_t)s * stride;
-    v[s] = (t >= lo && t < hi) ? ld(row + t) : 0ull;  // +0.0 outside the window
-  }
-#pragma unroll
-  for (int s = 0; s < C; ++s) pend |= (v[s] == kSentinel ? 1u : 0u) << s;
-  unsigned spins = 0;
-  while (pend != 0u || force_timeout) {
-    ++spins;
-    // a hand-off already failed in this launch (e.g. a split-basin peer that never arrives): give up
-    // at once instead of spinning out every later wait too
-    const bool failed = (spins & 1023u) == 0u &&
-                        __hip_atomic_load(status, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u;
-    if (force_timeout || failed || spins > (1u << 24)) {
-      atomicAdd(status, 1u);
-      atomicCAS(status + 1, 0u, (unsigned)bid + 1u);
-#pragma unroll
-      for (int s = 0; s < C; ++s) {
-        const int64_t t = t0 + (int64_t)s * stride;
-        const bool nan = ((pend >> s) & 1u) || (force_timeout && t >= lo && t < hi);
-        v[s] = nan ? 0x7FF8000000000000ull : v[s];
-      }
-      break;
-    }
-    __builtin_amdgcn_s_sleep(2);
-#pragma unroll
-    for (int s = 0; s < C; ++s) {
-      const unsigned long long w = ((pend >> s) & 1u) ? ld(row + (t0 + (int64_t)s * stride)) : v[s];
-      v[s] = w;
-      pend &= ~((w != kSentinel ? 1u : 0u) << s);
-    }
-  }
-#pragma unroll
-  for (int s = 0; s < C; ++s) out[s] = __longlong_as_double(v[s]);
-}
-
-// Split form of wait_granules for imports requested a chunk ahead: issue_granules requests the granules
-// (no wait: they land while the block runs on), poll_granules waits for the still-unpublished ones with the
-// same bounds and failure handling as wait_granules.
+// The bounded wait for granules, in two halves.  issue_granules requests row[t0 + s] (s < C; outside
+// [lo, hi): 0) all at once, so a chunk costs one memory round trip, not C; an import requested a chunk
+// ahead stops there, and its granules land while the block runs on.  poll_granules spins (bounded) until
+// the still-unpublished ones are published.  On a timeout (or with the debug flag that forces one) it
+// records it in the status block and returns NaN: the corruption then shows in the outputs.
 template <int C, bool Sys>
 __device__ __forceinline__ void issue_granules(const double* row, int64_t t0, int64_t lo, int64_t hi,
                                                unsigned long long (&v)[C]) {
 #pragma unroll
   for (int s = 0; s < C; ++s) {
     const int64_t t = t0 + s;
-    v[s] = (t >= lo && t < hi) ? (Sys ? load_granule_sys(row + t) : load_granule(row + t)) : 0ull;
+    v[s] = (t >= lo && t < hi) ? (Sys ? load_granule_sys(row + t) : load_granule(row + t)) : 0ull;  // +0.0 outside
   }
 }
 template <int C, bool Sys>
@@ -180,6 +136,52 @@ __device__ __forceinline__ void poll_granules(const double* row, int64_t t0, int
 #pragma unroll
     for (int s = 0; s < C; ++s) {
       const unsigned long long w = ((pend >> s) & 1u) ? ld(row + (t0 + s)) : v[s];
+      v[s] = w;
+      pend &= ~((w != kSentinel ? 1u : 0u) << s);
+    }
+  }
+#pragma unroll
+  for (int s = 0; s < C; ++s) out[s] = __longlong_as_double(v[s]);
+}
+// Request and wait at once.  It states poll_granules' loop a second time on purpose: as issue_granules +
+// poll_granules every backward instance compiles differently (the KR = 1 import waves merge the two inlined
+// polls; with `out` passed on through two references all instances reschedule), some with more spills.
+// Keep the two loops in step.
+template <int C, bool Sys = false>
+__device__ __forceinline__ void wait_granules(const double* row, int64_t t0, int64_t lo, int64_t hi,
+                                              double (&out)[C], unsigned* status, int bid, bool force_timeout) {
+  auto ld = [](const double* p) { return Sys ? load_granule_sys(p) : load_granule(p); };
+  unsigned long long v[C];
+  unsigned pend = 0;
+#pragma unroll
+  for (int s = 0; s < C; ++s) {
+    const int64_t t = t0 + (int64_t)s;
+    v[s] = (t >= lo && t < hi) ? ld(row + t) : 0ull;  // +0.0 outside the window
+  }
+#pragma unroll
+  for (int s = 0; s < C; ++s) pend |= (v[s] == kSentinel ? 1u : 0u) << s;
+  unsigned spins = 0;
+  while (pend != 0u || force_timeout) {
+    ++spins;
+    // a hand-off already failed in this launch (e.g. a split-basin peer that never arrives): give up
+    // at once instead of spinning out every later wait too
+    const bool failed = (spins & 1023u) == 0u &&
+                        __hip_atomic_load(status, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u;
+    if (force_timeout || failed || spins > (1u << 24)) {
+      atomicAdd(status, 1u);
+      atomicCAS(status + 1, 0u, (unsigned)bid + 1u);
+#pragma unroll
+      for (int s = 0; s < C; ++s) {
+        const int64_t t = t0 + (int64_t)s;
+        const bool nan = ((pend >> s) & 1u) || (force_timeout && t >= lo && t < hi);
+        v[s] = nan ? 0x7FF8000000000000ull : v[s];
+      }
+      break;
+    }
+    __builtin_amdgcn_s_sleep(2);
+#pragma unroll
+    for (int s = 0; s < C; ++s) {
+      const unsigned long long w = ((pend >> s) & 1u) ? ld(row + (t0 + (int64_t)s)) : v[s];
       v[s] = w;
       pend &= ~((w != kSentinel ? 1u : 0u) << s);
     }
@@ -260,16 +262,34 @@ __device__ __forceinline__ ReachStatic<R> load_static(const RouteArgs& a, int re
 // confluence (nup > 2) the offset of its list [c, u1, ..., u_{c-1}] in the block's LDS copy of
 // xlist: every upstream index of a tick comes from registers or LDS, never from a global load (whose
 // wait would also drain the tick's prefetches, in-order vmcnt).
-__device__ __forceinline__ unsigned pack_up(const RouteArgs& a, int P, unsigned none = 0u) {
-  const int b = a.s.upb[P], c = a.s.upc[P];
-  const unsigned u0 = c > 0 ? (unsigned)a.s.uplist[b] : none;
-  const unsigned u1 = c > 2 ? (unsigned)a.s.xoff[P] : (c > 1 ? (unsigned)a.s.uplist[b + 1] : none);
+__device__ __forceinline__ unsigned pack_up(const DevSchedule& s, int P, unsigned none = 0u) {
+  const int b = s.upb[P], c = s.upc[P];
+  const unsigned u0 = c > 0 ? (unsigned)s.uplist[b] : none;
+  const unsigned u1 = c > 2 ? (unsigned)s.xoff[P] : (c > 1 ? (unsigned)s.uplist[b + 1] : none);
   return u0 | (u1 << 13) | ((unsigned)(c < 15 ? c : 15) << 26);
 }
 // Copy the block's confluence lists into LDS (all threads; the caller synchronises).
-__device__ __forceinline__ void load_xlist(const RouteArgs& a, const BlockDesc& B, int* xl) {
-  for (int i = threadIdx.x; i < B.nxl; i += blockDim.x) xl[i] = a.s.xlist[B.xl0 + i];
+__device__ __forceinline__ void load_xlist(const DevSchedule& s, const BlockDesc& B, int* xl) {
+  for (int i = threadIdx.x; i < B.nxl; i += blockDim.x) xl[i] = s.xlist[B.xl0 + i];
 }
+// A forward kernel's schedule words of internal position P (block B, S slots per buffer).
+// off: the tick offset (low 16 bits: tick_off) | 1 + rank among the block's cut reaches (high 16: cut_rank,
+// 0 = not cut; its boundary granule row is B.cout0 + rank, graph.cpp numbers cut edges that way).
+// up: pack_up with the zero slot S - 1 for a missing upstream, which then adds exactly 0.
+struct ReachWords {
+  int ref, off;
+  unsigned up;
+};
+__device__ __forceinline__ ReachWords reach_words(const DevSchedule& s, const BlockDesc& B, int P, int S) {
+  ReachWords w;
+  w.ref = s.ref[P];
+  const int e = s.cut[P];
+  w.off = s.off[P] | (e >= 0 ? (e - B.cout0 + 1) << 16 : 0);
+  w.up = pack_up(s, P, (unsigned)(S - 1));
+  return w;
+}
+__device__ __forceinline__ int tick_off(int off) { return off & 0xFFFF; }
+__device__ __forceinline__ int cut_rank(int off) { return off >> 16; }
 // Make a per-reach value opaque inside the tick loop so the compiler recomputes what it derives
 // from it (64-bit addresses, qe + 1, ...) each tick instead of hoisting and keeping it live: at
 // KR reaches per thread the hoisted copies, not the state, exhaust the register file.
@@ -293,6 +313,44 @@ __device__ __forceinline__ int up_0(unsigned u) { return (int)(u & 8191u); }
 __device__ __forceinline__ int up_f1(unsigned u) { return (int)((u >> 13) & 8191u); }
 // slot of the second upstream (a confluence's from its LDS list)
 __device__ __forceinline__ int up_1(unsigned u, const int* xl) { return up_n(u) > 2 ? xl[up_f1(u) + 1] : up_f1(u); }
+
+// The forward kernels' virtual inflows (x of another block's reach, through cut edge v_edge): virtual vi is
+// imported and published by thread kBlockThreads - 1 - vi.  The owners sit in the last waves, which hold fewer
+// wave-slices than wave 0 when nloc is not a multiple of the workgroup (the import's global round trip lands
+// on the lighter waves); only the owner reads its ring entries [vi][kChunkFwd], so the import needs no
+// workgroup barrier.
+struct VirtOwner {
+  int vi, v_off, v_edge;
+  bool own;
+  __device__ __forceinline__ VirtOwner(const DevSchedule& s, const BlockDesc& B)
+      : vi(kBlockThreads - 1 - (int)threadIdx.x), v_off(0), v_edge(0), own(vi < B.nvirt) {
+    if (own) {
+      v_off = s.v_off[B.virt0 + vi];
+      v_edge = s.v_edge[B.virt0 + vi];
+    }
+  }
+  // The chunk of ticks [tau, tau + kChunkFwd) from the edge's granule row of `len` steps into the ring,
+  // requested and waited for now, kImportBatch granules at a time (owners only)
+  template <bool Sys>
+  __device__ __forceinline__ void import_chunk(const double* row, int64_t len, int tau, double* ring, unsigned* status, int bid,
+                                         bool force_timeout) const {
+#pragma unroll
+    for (int h = 0; h < kChunkFwd; h += kImportBatch) {
+      double g[kImportBatch];
+      wait_granules<kImportBatch, Sys>(row, (int64_t)tau - v_off + h, 0, len, g, status, bid, force_timeout);
+#pragma unroll
+      for (int i = 0; i < kImportBatch; ++i) ring[vi * kChunkFwd + h + i] = g[i];
+    }
+  }
+  // tick tau's value from the ring into the virtual's slot of buffer `dst` (after the block's nloc reaches)
+  template <typename Len>
+  __device__ __forceinline__ void publish(int tau, Len len, const double* ring, double* dst, int nloc) const {
+    if (own) {
+      const int t = tau - v_off;
+      if (t >= 0 && t < len) dst[nloc + vi] = ring[vi * kChunkFwd + (tau % kChunkFwd)];
+    }
+  }
+};
 
 // Debug per-workgroup profile (ddr_set_block_profile): start, end, import wait, hardware id.
 // Layout per workgroup: kProfWords uint64 = start, end, wait, hwid, then a timestamp every 1024 ticks.

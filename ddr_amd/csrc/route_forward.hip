@@ -49,10 +49,11 @@ __global__ void __launch_bounds__(kBlockThreads, kBlocksPerCU * kBlockThreads / 
   // between two barriers
   constexpr int kXBuf = XB > 0 ? XB : fwd_xbuf(KR);
   constexpr bool kDbl = kXBuf == 2;
-  double* sx = reinterpret_cast<double*>(smem + kMathTabBytes);         // [kXBuf][S] x_j(t), solve precision
-  const StatTab<R> tab{reinterpret_cast<R*>(sx + kXBuf * S)};           // [S][6]
-  double* ring = reinterpret_cast<double*>(smem + kMathTabBytes + align16(size_t(S) * (8 * kXBuf + 6 * sizeof(R))));  // [nvirt][kChunkFwd]
-  int* xl = reinterpret_cast<int*>(smem + a.xl_off);                     // confluence lists
+  const FwdLds<R> lds = fwd_lds<R>(smem, S, kXBuf);
+  double* sx = lds.x;              // [kXBuf][S] x_j(t), solve precision
+  const StatTab<R> tab{lds.stat};  // [S][6]
+  double* ring = lds.ring;         // [nvirt][kChunkFwd]
+  int* xl = reinterpret_cast<int*>(smem + a.xl_off);  // confluence lists
   const Consts<R> cs = consts_of<R>(a, !kFast && !kFaith, KR >= kOpqInfMinKR);
   const int64_t T = a.T;
   const bool carry = a.flags & DDR_FWD_CARRY;
@@ -65,11 +66,10 @@ __global__ void __launch_bounds__(kBlockThreads, kBlocksPerCU * kBlockThreads / 
   const R* q0p = static_cast<const R*>(a.q0);
   const int64_t xs_base = T * B.pos0 + B.pre_dn;
 
-  // off: tick offset (low 16 bits) | 1 + rank among the block's cut reaches (high 16, 0 = not cut;
-  // its boundary granule row is B.cout0 + rank, graph.cpp numbers cut edges that way)
+  // the schedule words of each reach (reach_words)
   int ref[KR], off[KR];
   unsigned up[KR];
-  auto off_of = [&](int k) { return off[k] & 0xFFFF; };
+  auto off_of = [&](int k) { return tick_off(off[k]); };
   R Q[KR], In[KR], qa[KR], qb[KR], ex[KR], inv[KR];  // ex, inv: the static divisions, kept in registers
   // one reach per thread (small blocks: light loads, where a tick is one dependency chain long): the
   // statics stay in registers, off the chain's LDS round trips
@@ -95,21 +95,21 @@ __global__ void __launch_bounds__(kBlockThreads, kBlocksPerCU * kBlockThreads / 
   const bool storer_mode = KR == 1 && !(a.flags & kFlagNoStorer) && B.nloc <= BS / 2;
   const bool storer_wave = storer_mode && wbase >= BS / 2;
   const int sr = tid - BS / 2;  // a storer thread's reach
-  int sref = 0, soff = 0;  // soff: tick offset | 1 + cut rank << 16, as off[]
+  int sref = 0, soff = 0;  // its ref and off words
   if (storer_wave && sr < B.nloc) {
-    sref = a.s.ref[B.pos0 + sr];
-    const int e = a.s.cut[B.pos0 + sr];
-    soff = a.s.off[B.pos0 + sr] | (e >= 0 ? (e - B.cout0 + 1) << 16 : 0);
+    const ReachWords w = reach_words(a.s, B, B.pos0 + sr, S);
+    sref = w.ref;
+    soff = w.off;
   }
 #pragma unroll
   for (int k = 0; k < KR; ++k) {
     const int r = tid + k * BS;
     const bool hk = r < B.nloc;
     const int P = B.pos0 + (hk ? r : 0);
-    ref[k] = a.s.ref[P];
-    const int e = a.s.cut[P];
-    off[k] = a.s.off[P] | (e >= 0 ? (e - B.cout0 + 1) << 16 : 0);
-    up[k] = pack_up(a, P, (unsigned)(S - 1));  // slot S-1 holds 0: missing upstreams add exactly 0
+    const ReachWords w = reach_words(a.s, B, P, S);
+    ref[k] = w.ref;
+    off[k] = w.off;
+    up[k] = w.up;
     Q[k] = In[k] = R(0);
     qa[k] = qb[k] = R(0);
     ob0[k] = ob1[k] = ob2[k] = ob3[k] = R(0);
@@ -121,10 +121,9 @@ __global__ void __launch_bounds__(kBlockThreads, kBlocksPerCU * kBlockThreads / 
   }
   if (tid == 0) sx[S - 1] = 0.0;
   if (kDbl && tid == 0) sx[2 * S - 1] = 0.0;
-  // virtual inflow vi is imported and published by thread BS - 1 - vi: the owners sit in the last
-  // waves, which hold fewer wave-slices than wave 0 when nloc is not a multiple of 1024 (the import's
-  // global round trip lands on the lighter waves; only the owner reads its ring entries, so the import
-  // needs no workgroup barrier)
+  // virtual inflow vi is imported and published by thread BS - 1 - vi (route_device.h, VirtOwner, says why
+  // there).  Its own scalars and its own import and publish text, not VirtOwner's: with the four words in a
+  // struct the KR = 4 instances change their scalar spills, one of them upwards
   const int vi = BS - 1 - tid;
   const bool vown = vi < B.nvirt;
   int v_off = 0, v_edge = 0;
@@ -133,7 +132,7 @@ __global__ void __launch_bounds__(kBlockThreads, kBlocksPerCU * kBlockThreads / 
     v_edge = a.s.v_edge[B.virt0 + vi];
   }
   load_math_tables();
-  load_xlist(a, B, xl);
+  load_xlist(a.s, B, xl);
   uintptr_t* xt = reinterpret_cast<uintptr_t*>(smem + xt_off);  // split: cut-outs' export rows
   if (xt_off) {
     for (int c = tid; c < B.ncout; c += BS) {
@@ -175,14 +174,14 @@ __global__ void __launch_bounds__(kBlockThreads, kBlocksPerCU * kBlockThreads / 
   auto store_pass = [&](int taup) {
     if (sr >= B.nloc) return;
     const int so = opq(soff);
-    const int t = taup - (so & 0xFFFF);
+    const int t = taup - tick_off(so);
     if (t < 0 || t >= T) return;
     const double xd = sx[(kDbl ? (taup & 1) * S : 0) + sr];
     const R xr = R(xd);
-    if (B.ncout > 0 && (so >> 16)) {
-      const int64_t e = B.cout0 + (so >> 16) - 1;
+    if (B.ncout > 0 && cut_rank(so)) {
+      const int64_t e = B.cout0 + cut_rank(so) - 1;
       if (xt_off) {
-        const uintptr_t p = xt[(so >> 16) - 1];
+        const uintptr_t p = xt[cut_rank(so) - 1];
         double* row = reinterpret_cast<double*>(p & ~uintptr_t(1));
         if (p & 1u) store_granule_sys(row + t, xd);
         else store_granule(row + t, xd);
@@ -235,7 +234,7 @@ __global__ void __launch_bounds__(kBlockThreads, kBlocksPerCU * kBlockThreads / 
 #pragma unroll
           for (int h = 0; h < kChunkFwd; h += kImportBatch) {
             double g[kImportBatch];
-            wait_granules<kImportBatch, true>(a.xfwd + (int64_t)xi * T, (int64_t)tau - v_off + h, 1, 0, T, g, a.status,
+            wait_granules<kImportBatch, true>(a.xfwd + (int64_t)xi * T, (int64_t)tau - v_off + h, 0, T, g, a.status,
                                               bid, force_to);
 #pragma unroll
             for (int i = 0; i < kImportBatch; ++i) ring[vi * kChunkFwd + h + i] = g[i];
@@ -244,7 +243,7 @@ __global__ void __launch_bounds__(kBlockThreads, kBlocksPerCU * kBlockThreads / 
 #pragma unroll
           for (int h = 0; h < kChunkFwd; h += kImportBatch) {
             double g[kImportBatch];
-            wait_granules<kImportBatch>(a.bnd + (int64_t)v_edge * T, (int64_t)tau - v_off + h, 1, 0, T, g, a.status,
+            wait_granules<kImportBatch>(a.bnd + (int64_t)v_edge * T, (int64_t)tau - v_off + h, 0, T, g, a.status,
                                         bid, force_to);
 #pragma unroll
             for (int i = 0; i < kImportBatch; ++i) ring[vi * kChunkFwd + h + i] = g[i];
@@ -401,10 +400,10 @@ __global__ void __launch_bounds__(kBlockThreads, kBlocksPerCU * kBlockThreads / 
             if (!emit4) orow[t] = ob3[k];
             else if ((t & 3) == 3) store4(orow + (t - 3), ob0[k], ob1[k], ob2[k], ob3[k]);
           }
-          if (B.ncout > 0 && (off[k] >> 16) && !storer_mode) {
-            const int64_t e = B.cout0 + (off[k] >> 16) - 1;
+          if (B.ncout > 0 && cut_rank(off[k]) && !storer_mode) {
+            const int64_t e = B.cout0 + cut_rank(off[k]) - 1;
             if (xt_off) {  // split basin: the row from the block's table (another rank's: system scope)
-              const uintptr_t p = xt[(off[k] >> 16) - 1];
+              const uintptr_t p = xt[cut_rank(off[k]) - 1];
               double* row = reinterpret_cast<double*>(p & ~uintptr_t(1));
               if (p & 1u) store_granule_sys(row + t, x);
               else store_granule(row + t, x);
@@ -608,21 +607,12 @@ hipError_t launch_forward_kr(const Graph* g, RouteArgs a, hipStream_t stream) {
 
 template <typename R>
 hipError_t launch_route_forward(const Graph* g, const RouteArgs& a, hipStream_t stream) {
-  switch (g->kr) {
-    case 1: return launch_forward_kr<R, 1>(g, a, stream);
-    case 2: return launch_forward_kr<R, 2>(g, a, stream);
-    default: return launch_forward_kr<R, 4>(g, a, stream);
-  }
+  return dispatch_kr(g, [&](auto kr) { return launch_forward_kr<R, decltype(kr)::value>(g, a, stream); });
 }
 
 template <typename R>
 int forward_resident_blocks(const Graph* g) {
-  const void* f = nullptr;
-  switch (g->kr) {
-    case 1: f = (const void*)route_forward_kernel<R, 1, 0>; break;
-    case 2: f = (const void*)route_forward_kernel<R, 2, 0>; break;
-    default: f = (const void*)route_forward_kernel<R, 4, 0>;
-  }
+  const void* f = dispatch_kr(g, [](auto kr) { return (const void*)route_forward_kernel<R, decltype(kr)::value, 0>; });
   return resident_blocks(g, f, route_lds_plan<R>(g, false, 0).smem);
 }
 

@@ -1,9 +1,9 @@
-// Host side of a routing launch, shared by route_forward.hip and route_backward.h: the dynamic-LDS
-// plan (one definition for the launches, the backward's buffer choice and the occupancy queries) and
-// the launch geometry.
+// Host side of a routing launch, shared by route_forward.hip, route_linear.hip and route_backward.h: the
+// dynamic-LDS plan (one definition for the launches, the backward's buffer choice and the occupancy queries),
+// the launch geometry and the dispatch on the graph's reaches per thread.
 #pragma once
 
-#include <algorithm>
+#include <type_traits>
 
 #include "internal.h"
 #include "route_args.h"
@@ -33,19 +33,34 @@ RouteLds route_lds_plan(const Graph* g, bool backward, int xb) {
                            (size_t)g->max_xl, backward, sizeof(R), g->kr, xb);
   p.smem = align16(p.base) + split_table_bytes(g, backward);
   p.xl_off = (int32_t)(p.base - (size_t)g->max_xl * 4);  // the lists close the base LDS layout
-  p.own_off = p.xl_off - (int32_t)align16(4 * (size_t)std::max(g->max_virt, g->max_cout));
+  p.own_off = p.xl_off - (int32_t)route_own_bytes((size_t)g->max_virt, (size_t)g->max_cout, true);
   p.xt_off = g->split.nranks > 0 ? (int32_t)align16(p.base) : 0;
   return p;
 }
 
-// The launch arguments that follow from the graph and the plan
-inline void set_launch_args(RouteArgs& a, const Graph* g, const RouteLds& p) {
+// The launch arguments that follow from the graph and the plan: those of every kernel on the schedule
+// (RouteArgs, LinArgs), then the Muskingum-Cunge kernels' own
+template <typename Args>
+void set_schedule_args(Args& a, const Graph* g, const RouteLds& p) {
   a.slot_stride = route_slot_stride(g->max_slots);
-  a.n_cut = g->n_cut;
   a.nblocks = (int32_t)g->blocks.size();
   a.xl_off = p.xl_off;
+}
+inline void set_launch_args(RouteArgs& a, const Graph* g, const RouteLds& p) {
+  set_schedule_args(a, g, p);
+  a.n_cut = g->n_cut;
   a.own_off = p.own_off;
   a.xt_off = p.xt_off;
+}
+
+// f(std::integral_constant<int, KR>{}) for the graph's reaches per thread (1, 2 or 4: kr_of_load)
+template <typename F>
+auto dispatch_kr(const Graph* g, F&& f) {
+  switch (g->kr) {
+    case 1: return f(std::integral_constant<int, 1>{});
+    case 2: return f(std::integral_constant<int, 2>{});
+    default: return f(std::integral_constant<int, 4>{});
+  }
 }
 
 // Workgroups of kernel `f` resident on the device with `smem` bytes of dynamic LDS each (-1: query failed)

@@ -1,6 +1,8 @@
 // Linear Muskingum routing, RAPID's matrix scheme, on the Muskingum-Cunge forward's schedule: per-reach
 // constant (k, x), the same sparse lower-triangular solve per sub-step, no physics.  One persistent launch
-// routes all F * S sub-steps.  The schedule, the hand-offs and the shared device helpers: route_device.h.
+// routes all F * S sub-steps.  Shared with that forward, from route_device.h, internal.h and route_launch.h:
+// the schedule and its per-reach words, the LDS layout, the virtual-inflow owner and its bounded waits, the
+// launch plan.  Its own: the tick below (one general tick, no physics) and the interval outputs.
 //
 // Per reach, in the routed precision R, separately rounded operations (no contraction):
 //   h = dt / 2, den = k (1 - x) + h, C1 = (h - k x) / den, C2 = (h + k x) / den, C3 = (k (1 - x) - h) / den
@@ -19,18 +21,6 @@
 
 namespace ddr {
 
-namespace {
-
-// the packed upstream word of route_device.h (pack_up) from the schedule alone
-__device__ __forceinline__ unsigned lin_pack_up(const DevSchedule& s, int P, unsigned none) {
-  const int b = s.upb[P], c = s.upc[P];
-  const unsigned u0 = c > 0 ? (unsigned)s.uplist[b] : none;
-  const unsigned u1 = c > 2 ? (unsigned)s.xoff[P] : (c > 1 ? (unsigned)s.uplist[b + 1] : none);
-  return u0 | (u1 << 13) | ((unsigned)(c < 15 ? c : 15) << 26);
-}
-
-}  // namespace
-
 template <typename R, int KR>
 __global__ void __launch_bounds__(kBlockThreads, kBlocksPerCU * kBlockThreads / 256) route_linear_kernel(LinArgs a) {
   constexpr int BS = kBlockThreads;
@@ -40,13 +30,14 @@ __global__ void __launch_bounds__(kBlockThreads, kBlocksPerCU * kBlockThreads / 
   const int tid = threadIdx.x;
   const int wbase = __builtin_amdgcn_readfirstlane(tid & ~63);
   const int S = a.slot_stride;
-  // the forward's LDS plan (route_lds_plan): x slots (fp64, by tick parity at KR <= 2: one barrier per tick)
-  // | per-reach statics, here [S][4] = C1, C2, C3 | import ring | confluence lists
+  // the forward's LDS layout (fwd_lds; x slots by tick parity at KR <= 2: one barrier per tick); the statics
+  // region holds the coefficient table [S][kLinCoefs] = C1, C2, C3, 0
   constexpr int kXBuf = fwd_xbuf(KR);
   constexpr bool kDbl = kXBuf == 2;
-  double* sx = reinterpret_cast<double*>(smem + kMathTabBytes);
-  R* ctab = reinterpret_cast<R*>(sx + kXBuf * S);
-  double* ring = reinterpret_cast<double*>(smem + kMathTabBytes + align16(size_t(S) * (8 * kXBuf + 6 * sizeof(R))));
+  const FwdLds<R> lds = fwd_lds<R>(smem, S, kXBuf);
+  double* sx = lds.x;
+  R* ctab = lds.stat;
+  double* ring = lds.ring;
   int* xl = reinterpret_cast<int*>(smem + a.xl_off);
   const int TS = a.TS;
   const int sub1 = a.S - 1;
@@ -60,10 +51,10 @@ __global__ void __launch_bounds__(kBlockThreads, kBlocksPerCU * kBlockThreads / 
   R* qlast = static_cast<R*>(a.q_last);
   const double dsub = (double)a.S;
 
-  // off: tick offset (low 16 bits) | 1 + rank among the block's cut reaches (high 16), as the forward's
+  // the schedule words of each reach (reach_words)
   int ref[KR], off[KR];
   unsigned up[KR];
-  auto off_of = [&](int k) { return off[k] & 0xFFFF; };
+  auto off_of = [&](int k) { return tick_off(off[k]); };
   // per-tick state: Q, the previous sub-step's upstream sum, the interval's fp64 sum; the forcing row of the
   // current step and the sub-step within it (advanced without a division)
   R Q[KR], In[KR], qa[KR], qb[KR];
@@ -80,10 +71,10 @@ __global__ void __launch_bounds__(kBlockThreads, kBlocksPerCU * kBlockThreads / 
     const int r = tid + k * BS;
     const bool hk = r < B.nloc;
     const int P = B.pos0 + (hk ? r : 0);
-    ref[k] = a.s.ref[P];
-    const int e = a.s.cut[P];
-    off[k] = a.s.off[P] | (e >= 0 ? (e - B.cout0 + 1) << 16 : 0);
-    up[k] = lin_pack_up(a.s, P, (unsigned)(S - 1));  // slot S - 1 holds 0: a missing upstream adds exactly 0
+    const ReachWords w = reach_words(a.s, B, P, S);
+    ref[k] = w.ref;
+    off[k] = w.off;
+    up[k] = w.up;
     Q[k] = In[k] = qa[k] = qb[k] = R(0);
     acc[k] = 0.0;
     fr[k] = ph[k] = 0;
@@ -94,7 +85,7 @@ __global__ void __launch_bounds__(kBlockThreads, kBlocksPerCU * kBlockThreads / 
       const R kx = kk * xx;
       const R k1 = kk * (R(1) - xx);
       const R den = k1 + h;
-      R* c = ctab + 4 * r;
+      R* c = ctab + kLinCoefs * r;
       c[0] = (h - kx) / den;
       c[1] = (h + kx) / den;
       c[2] = (k1 - h) / den;
@@ -103,15 +94,8 @@ __global__ void __launch_bounds__(kBlockThreads, kBlocksPerCU * kBlockThreads / 
   }
   if (tid == 0) sx[S - 1] = 0.0;
   if (kDbl && tid == 0) sx[2 * S - 1] = 0.0;
-  // virtual inflow vi is imported and published by thread BS - 1 - vi (only the owner reads its ring entries)
-  const int vi = BS - 1 - tid;
-  const bool vown = vi < B.nvirt;
-  int v_off = 0, v_edge = 0;
-  if (vown) {
-    v_off = a.s.v_off[B.virt0 + vi];
-    v_edge = a.s.v_edge[B.virt0 + vi];
-  }
-  for (int i = tid; i < B.nxl; i += BS) xl[i] = a.s.xlist[B.xl0 + i];
+  const VirtOwner vo(a.s, B);
+  load_xlist(a.s, B, xl);
   __syncthreads();
 
   // the forcing of the step each reach runs at tick `tau` (the gathered row of its interval; the carried
@@ -132,23 +116,10 @@ __global__ void __launch_bounds__(kBlockThreads, kBlocksPerCU * kBlockThreads / 
 
   // the next chunk of every virtual inflow (x of the upstream block's reach), at ticks 0 mod kChunkFwd
   auto import_chunk = [&](int tau) {
-    if (B.nvirt > 0 && (tau % kChunkFwd) == 0 && vown) {
-#pragma unroll
-      for (int h = 0; h < kChunkFwd; h += kImportBatch) {
-        double g[kImportBatch];
-        wait_granules<kImportBatch>(a.bnd + (int64_t)v_edge * TS, (int64_t)tau - v_off + h, 1, 0, TS, g, a.status, bid,
-                                    force_to);
-#pragma unroll
-        for (int i = 0; i < kImportBatch; ++i) ring[vi * kChunkFwd + h + i] = g[i];
-      }
-    }
+    if (B.nvirt > 0 && (tau % kChunkFwd) == 0 && vo.own)
+      vo.import_chunk<false>(a.bnd + (int64_t)vo.v_edge * TS, TS, tau, ring, a.status, bid, force_to);
   };
-  auto publish_virt = [&](int tau, double* dst) {
-    if (vown) {
-      const int t = tau - v_off;
-      if (t >= 0 && t < TS) dst[B.nloc + vi] = ring[vi * kChunkFwd + (tau % kChunkFwd)];
-    }
-  };
+  auto publish_virt = [&](int tau, double* dst) { vo.publish(tau, TS, ring, dst, B.nloc); };
 
   auto tick = [&](int tau, R(&qcur)[KR], R(&qnext)[KR]) {
     // the previous tick's prefetch and stores land here (as the forward's tick)
@@ -195,7 +166,7 @@ __global__ void __launch_bounds__(kBlockThreads, kBlocksPerCU * kBlockThreads / 
           hot = hot + xj;
         }
       }
-      const R* c = ctab + 4 * (hk ? r : 0);
+      const R* c = ctab + kLinCoefs * (hk ? r : 0);
       const R c1 = c[0], c2 = c[1], c3 = c[2];
       const R Qr = ((c1 * (inn + qe)) + (c2 * (In[k] + qe))) + (c3 * Q[k]);
       // step 0: the initial state (qcur holds q0 there when one is given)
@@ -227,8 +198,8 @@ __global__ void __launch_bounds__(kBlockThreads, kBlocksPerCU * kBlockThreads / 
           ph[k] = wrap ? 0 : ph[k] + 1;
           fr[k] = fr[k] + (wrap ? 1 : 0);
         }
-        if (B.ncout > 0 && (off[k] >> 16)) {
-          const int64_t e = B.cout0 + (off[k] >> 16) - 1;
+        if (B.ncout > 0 && cut_rank(off[k])) {
+          const int64_t e = B.cout0 + cut_rank(off[k]) - 1;
           store_granule(a.bnd + e * TS + t, x);
         }
         Q[k] = Qn;
@@ -277,9 +248,7 @@ __global__ void linear_gauge_kernel(int64_t G, int64_t F, const int64_t* goff, c
 template <typename R, int KR>
 static hipError_t launch_linear_kr(const Graph* g, LinArgs a, hipStream_t stream) {
   const RouteLds lds = route_lds_plan<R>(g, false, 0);
-  a.slot_stride = route_slot_stride(g->max_slots);
-  a.nblocks = (int32_t)g->blocks.size();
-  a.xl_off = lds.xl_off;
+  set_schedule_args(a, g, lds);
   auto kern = route_linear_kernel<R, KR>;
   hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds.smem);
   if (e != hipSuccess) return e;
@@ -289,21 +258,12 @@ static hipError_t launch_linear_kr(const Graph* g, LinArgs a, hipStream_t stream
 
 template <typename R>
 hipError_t launch_route_linear(const Graph* g, LinArgs a, hipStream_t stream) {
-  switch (g->kr) {
-    case 1: return launch_linear_kr<R, 1>(g, a, stream);
-    case 2: return launch_linear_kr<R, 2>(g, a, stream);
-    default: return launch_linear_kr<R, 4>(g, a, stream);
-  }
+  return dispatch_kr(g, [&](auto kr) { return launch_linear_kr<R, decltype(kr)::value>(g, a, stream); });
 }
 
 template <typename R>
 int linear_resident_blocks(const Graph* g) {
-  const void* f = nullptr;
-  switch (g->kr) {
-    case 1: f = (const void*)route_linear_kernel<R, 1>; break;
-    case 2: f = (const void*)route_linear_kernel<R, 2>; break;
-    default: f = (const void*)route_linear_kernel<R, 4>;
-  }
+  const void* f = dispatch_kr(g, [](auto kr) { return (const void*)route_linear_kernel<R, decltype(kr)::value>; });
   return resident_blocks(g, f, route_lds_plan<R>(g, false, 0).smem);
 }
 

@@ -1,6 +1,6 @@
 """Worker of tests/test_gpu_split.py: one rank of a basin split across processes that share cuda:0
 (the single-GPU rehearsal of ddr_amd.split; the receive memory is exchanged by IPC handle exactly as
-across GPUs).  Usage: python tests/split_worker.py RANK WORLD PORT OUT.npz MATH"""
+across GPUs).  Usage: python tests/split_worker.py RANK WORLD PORT OUT.npz MATH [SHAPE]"""
 
 import os
 import sys
@@ -11,16 +11,20 @@ sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."
 
 N, T, SEED = 6000, 160, 21
 GRAPH_KW = {"max_block_reaches": 256, "target_blocks": 1 << 20}
+# (reaches, steps, partition).  "light": one reach per thread, imports requested a chunk ahead.  "full": three
+# blocks of four reaches per thread, imported with the batched wait, over a window that ends inside an import chunk
+SHAPES = {"light": (N, T, GRAPH_KW), "full": (4500, 7, {"max_block_reaches": 2400, "target_blocks": 1})}
 
 
-def case():
+def case(shape="light"):
     from ddr_amd import synthetic
 
-    net = synthetic.hack_basin(N, seed=SEED)
+    n, steps, _ = SHAPES[shape]
+    net = synthetic.hack_basin(n, seed=SEED)
     at = synthetic.reach_attributes(net.n, SEED)
     u = synthetic.unit_parameters(net.n, SEED)
-    qp = synthetic.lateral_inflow(net.n, T, SEED)
-    W = np.random.default_rng(SEED).uniform(0, 1, (net.n, T)).astype(np.float32)
+    qp = synthetic.lateral_inflow(net.n, steps, SEED)
+    W = np.random.default_rng(SEED).uniform(0, 1, (net.n, steps)).astype(np.float32)
     return net, at, u, qp, W
 
 
@@ -59,6 +63,7 @@ def second_inputs(qp):
 
 def main():
     rank, world, port, out, math = int(sys.argv[1]), int(sys.argv[2]), int(sys.argv[3]), sys.argv[4], sys.argv[5]
+    shape = sys.argv[6] if len(sys.argv) > 6 else "light"
     import ctypes as C
 
     import torch
@@ -72,8 +77,8 @@ def main():
     dist.init_process_group("gloo", init_method=f"tcp://127.0.0.1:{port}", rank=rank, world_size=world)
     torch.cuda.set_device(0)
     dev = torch.device("cuda", 0)
-    net, at, u, qp, W = case()
-    g = RiverGraph(net.n, net.rows, net.cols, **GRAPH_KW)
+    net, at, u, qp, W = case(shape)
+    g = RiverGraph(net.n, net.rows, net.cols, **SHAPES[shape][2])
     nloc, prod, cons = block_edges(g)
     br = plan_block_ranks(nloc, world, prod, cons)
 
@@ -82,7 +87,7 @@ def main():
         dist.all_gather_object(res, obj)
         return res
 
-    sb = SplitBasin(g, br, rank, world, T, exchange)
+    sb = SplitBasin(g, br, rank, world, SHAPES[shape][1], exchange)
     res = [route_once(g, net, at, u, qp, W, math, dev) for _ in range(2)]  # two launches: epochs advance
     check_status()
     # forward A, forward B, backward A, backward B: forward B rewrites the shared receive rows before

@@ -169,6 +169,26 @@ def test_faithful_partition_invariance_with_full_workgroups(cuda):
             np.testing.assert_array_equal(alt[k], big[k])
 
 
+@pytest.mark.parametrize("T", [5, 6, 7])
+def test_full_workgroup_imports_at_ragged_windows(cuda, T):
+    """One basin cut into blocks of four reaches per thread imports its cut edges with the batched wait, a chunk
+    of four ticks at a time; a window that ends inside such a chunk routes bitwise like the same basin at one
+    reach per thread (imports requested a chunk ahead), forward and gradients, exact and faithful."""
+    net = synthetic.hack_basin(4500, seed=21)
+    case = synthetic_case(net, T, 21)
+    for math in ("exact", "faithful"):
+        big = run_hip(case, cuda, gkw={"max_block_reaches": 2400, "target_blocks": 1}, math=math)
+        assert big["graph"].info.reaches_per_thread == 4 and big["graph"].info.n_cut > 0
+        one = run_hip(case, cuda, gkw={"max_block_reaches": 256, "target_blocks": 1 << 20}, math=math)
+        assert one["graph"].info.reaches_per_thread == 1 and one["graph"].info.n_cut > 0
+        for k in ("runoff", "q_last", "grad_n", "grad_q_spatial", "grad_p_spatial"):
+            np.testing.assert_array_equal(big[k], one[k], err_msg=f"{math} {k}")
+        if math == "exact":  # the oracle's recipe, at the bar of test_fp32_matches_oracle_recipe
+            ref = O.route(case.network(), big["reaches"], case.qprime, case.bounds, dtype=np.float32)
+            assert maxrel(big["runoff"], ref["runoff"]) <= 1e-6
+            assert maxrel(big["q_last"], ref["q_last"]) <= 1e-6
+
+
 def test_basin_independence(cuda):
     """Routing a subset of basins alone equals routing them inside the full forest (bitwise)."""
     from ddr_amd.partition import basin_labels, extract_basins

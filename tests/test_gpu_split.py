@@ -26,20 +26,26 @@ def _free_port():
     return p
 
 
-@pytest.mark.parametrize("math,world", [("exact", 2), ("faithful", 2), ("exact", 3)])
-def test_split_basin_processes_bitwise(cuda, tmp_path, math, world):
+@pytest.mark.parametrize("math,world,shape", [("exact", 2, "light"), ("faithful", 2, "light"), ("exact", 3, "light"),
+                                              ("faithful", 2, "full")],
+                         ids=["exact-2", "faithful-2", "exact-3", "faithful-2-full"])
+def test_split_basin_processes_bitwise(cuda, tmp_path, math, world, shape):
     from ddr_amd.graph import RiverGraph
 
-    net, at, u, qp, Wt = W.case()
-    g = RiverGraph(net.n, net.rows, net.cols, **W.GRAPH_KW)
-    assert g.info.n_blocks >= 4 and g.info.n_cut > 0
+    net, at, u, qp, Wt = W.case(shape)
+    g = RiverGraph(net.n, net.rows, net.cols, **W.SHAPES[shape][2])
+    assert g.info.n_cut > 0
+    if shape == "light":
+        assert g.info.n_blocks >= 4
+    else:
+        assert g.info.n_blocks > world and g.info.reaches_per_thread == 4
     ref = W.route_once(g, net, at, u, qp, Wt, math, cuda)
     ref_b = W.route_once(g, net, at, u, W.second_inputs(qp), Wt, math, cuda)
     port = _free_port()
     outs = [str(tmp_path / f"r{r}.npz") for r in range(world)]
     env = dict(os.environ, PYTHONUNBUFFERED="1")
     procs = [subprocess.Popen([sys.executable, os.path.join(HERE, "split_worker.py"), str(r), str(world), str(port),
-                               outs[r], math], env=env, stdout=subprocess.PIPE, stderr=subprocess.STDOUT)
+                               outs[r], math, shape], env=env, stdout=subprocess.PIPE, stderr=subprocess.STDOUT)
              for r in range(world)]
     logs = []
     for p in procs:
