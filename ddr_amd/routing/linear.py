@@ -49,6 +49,34 @@ def muskingum_coefficients(k, x, dt):
     return (h - kx) / den, (h + kx) / den, (k1 - h) / den
 
 
+def muskingum_coefficient_gradients(k, x, dt):
+    """Closed-form derivatives of :func:`muskingum_coefficients`: ``((dC1/dk, dC2/dk, dC3/dk), (dC1/dx, dC2/dx,
+    dC3/dx))``, with ``h = dt / 2`` and ``den = k (1 - x) + h``::
+
+        dC/dk = (-h, h (2 x - 1), 2 h (1 - x)) / den^2        dC/dx = (-k^2, k (k + 2 h), -2 h k) / den^2
+
+    Always evaluated and returned in float64, whatever the dtype of ``k``: each set sums to zero (C1 + C2 + C3 = 1),
+    so a parameter gradient ``sum_j dL/dC_j dC_j/dk`` is the remainder of cancelling terms and is to be combined in
+    fp64 and rounded once.  Tensors (host or device) give tensors, anything else NumPy arrays; ``h`` is taken from
+    ``dt`` rounded as the routing rounds it, in the dtype of ``k``."""
+    if isinstance(k, torch.Tensor):
+        h = (torch.tensor(dt, dtype=k.dtype, device=k.device) / 2).to(torch.float64)
+        x = torch.as_tensor(x, dtype=k.dtype, device=k.device).to(torch.float64)
+        k = k.to(torch.float64)
+    else:
+        k = np.asarray(k)
+        if k.dtype not in (np.float32, np.float64):
+            k = k.astype(np.float64)
+        h = np.float64(k.dtype.type(dt) / k.dtype.type(2))
+        x = np.asarray(x, k.dtype).astype(np.float64)
+        k = k.astype(np.float64)
+    den = (k * (1.0 - x)) + h
+    d2 = den * den
+    dk = ((-h) / d2, (h * ((2.0 * x) - 1.0)) / d2, ((2.0 * h) * (1.0 - x)) / d2)
+    dx = ((-(k * k)) / d2, (k * (k + (2.0 * h))) / d2, (-((2.0 * h) * k)) / d2)
+    return dk, dx
+
+
 def rapid_parameters(ids, reach_ids, k, x, k_units: str = "seconds"):
     """RAPID's parameter files aligned to a network: ``k`` (seconds) and ``x`` of reach ``ids[i]``, looked up in
     ``reach_ids`` (the order of RAPID's ``k`` and ``x`` files), as float64 arrays in the order of ``ids``
